@@ -17,7 +17,7 @@ mi_interp1_f64_dev over the rank's 1e8 resident queries.  Inputs are generated i
 
 Multi-GPU: the query axis shards trivially: every rank owns its own 1e8-query shard and a
 replica of the table; there is no data-path collective in the timed region ("scaling": "weak").  The optional
-all-gather that reassembles the full result vector on every rank is timed separately (extra.allgather_ms).
+all-gather that reassembles the full result vector on every rank is timed separately (--full: extra.allgather_ms).
 
 What to expect from the headline, up front (profiles/r04_bench_rocprof_summary.json,
 profiles/r03_exp_gather_rate_vs_active_cus.log): uniformly random queries over a table larger than an XCD's L2 are bound by
@@ -26,9 +26,18 @@ least 0.44 ms: 46 % of 8 TB/s is the ceiling of any single-pass design on this m
 0.68 ms = 29.4 % (roofline.request_floor_ms_at_measured_cap carries the floor in every line).  north_star's >= 70 % holds for
 ordered query sets: extra.general_sorted (78.2 %), extra.general_uniformq (the set XI_j = j/(NQ-1): 77.7 %).
 
-Every line -- any N, --backend group, --config 3 -- carries cpu_baseline (the CPU oracle on this box's host cores: the whole
-1e8-query set at N = 1, a 2e7-query sample by rank 0 at N > 1), and at N > 1 extra.n1_reference_ms: rank 0 repeating the
-same step alone, so that the 1 -> N ratio can be formed from one line.
+A plain run sets up, warms up, times the K steps and prints its line: cpu_baseline is null and extra is empty.  With --full
+every line -- any N, --backend group, --config 3 -- also carries cpu_baseline (the CPU oracle on the host cores: the whole
+1e8-query set at N = 1, a 2e7-query sample by rank 0 at N > 1) and the secondary measurements (extra.*; at N > 1
+extra.n1_reference_ms: rank 0 repeating the same step alone, so that the 1 -> N ratio can be formed from one line, the
+all-gather time, and with --scaling strong the compute + all-gather loop).  --no-extra / --no-cpu-baseline leave parts
+of --full out.
+
+--dump-outputs DIR: right after the timed steps, the result vector of the last step is written as DIR/<name>.npy, float64:
+yi for the 1-D headline, zi for --config 3, yi_rank<r> / zi_rank<r> per rank at N > 1, yi_shard<r> per member of
+--backend group (and yi_gathered<r> with --gather).  The whole array when it fits in 32 MB in all, else the elements at a
+fixed sample of indices (one seeded index in each of equal strata), so that two builds of the project can be compared
+output for output on identical inputs.
 
 Rank 0 prints ONE JSON line (the last line of stdout).
 """
@@ -47,17 +56,24 @@ NQ = 100_000_000
 SEED_Q = 0x5EED0003
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 SWEEP_MIN_TILES_PER_CU = int(os.environ.get("MI_SWEEP_MIN_TILES_PER_CU", "2"))   # csrc/mi_interp1.hip kSweepMinTilesPerCu
+DUMP_BYTES = 32 << 20           # --dump-outputs: at most this many bytes of samples in all
+DUMP_SEED = 0x5EED00D0
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed steps before them")
     ap.add_argument("--nq", type=int, default=NQ, help="queries per GPU (default: BASELINE size 1e8)")
     ap.add_argument("--ng", type=int, default=NG)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements (sorted queries, "
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, also measure the CPU baseline and the secondary measurements (extra.*; at "
+                         "N > 1 the one-rank reference and the all-gather; --scaling strong: compute + all-gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result vector (or a fixed seeded sample of it) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary measurements (sorted queries, "
                     "implicit-uniform table, config 3, restrict+mean, all-gather)")
     ap.add_argument("--table", choices=["general", "uniform", "nonuniform"], default="general",
                     help="general: explicit X of configs[1] (detected closed form); uniform: implicit grid; nonuniform: "
@@ -69,8 +85,8 @@ def parse():
                     help="map every rank to cuda:0 (only with --dist-backend gloo; timings are then meaningless)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default, the contract's line): every rank its own --nq queries; strong: ONE set of --nq "
-                         "queries split into contiguous NQ/P shards (BASELINE.md section 2), compute-only and compute + "
-                         "all-gather both reported")
+                         "queries split into contiguous NQ/P shards (BASELINE.md section 2), compute-only reported, with "
+                         "--full also compute + all-gather")
     ap.add_argument("--shard-of", type=int, default=0, metavar="P",
                     help="1-GPU rehearsal of the strong-scaling shard sizes: time this GPU on shard 0 of P (NQ/P queries)")
     ap.add_argument("--force-dist", action="store_true",
@@ -88,7 +104,36 @@ def parse():
     ap.add_argument("--config", type=int, choices=[2, 3], default=2,
                     help="2 (default): BASELINE configs[1], the 1-D headline; 3: configs[2], 4096^2 bilinear, 1e8 scattered "
                          "queries as the timed workload (for profiling interp2_kernel; same JSON contract)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.extra = args.full and not args.no_extra
+    return args
+
+
+def sample_indices(n, k):
+    """k of the indices 0 .. n-1 (all of them when k >= n), increasing: k equal strata of the range, one index drawn in
+    each from a generator seeded with DUMP_SEED, so that the same (n, k) always gives the same indices."""
+    import numpy as np
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    lo = np.arange(k, dtype=np.int64) * n // k
+    hi = np.arange(1, k + 1, dtype=np.int64) * n // k
+    return lo + (np.random.default_rng(DUMP_SEED).random(k) * (hi - lo)).astype(np.int64)
+
+
+def dump_outputs(dirpath, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every (name, device tensor) of `arrays` as dirpath/<name>.npy; an array larger than its share of
+    `budget` is reduced to its elements at sample_indices."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    for name, t in arrays:
+        assert t.dtype in (torch.float32, torch.float64), (name, t.dtype)
+        t = t.reshape(-1)
+        if t.numel() > share // t.element_size():
+            t = t[torch.from_numpy(sample_indices(t.numel(), share // t.element_size())).to(t.device)]
+        np.save(os.path.join(dirpath, name + ".npy"), t.cpu().numpy())
 
 
 def timed_loop(ctx, fn, steps, warmup, barrier):
@@ -237,6 +282,8 @@ def bench_config3(args, ctx, info, dev, world, rank, barrier, dist, dist_on):
     zq = torch.empty(nq, dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
     wall, ev = timed_loop(ctx, lambda: g2.interp(q2[:nq], q2[nq:], out=zq), args.steps, args.warmup, barrier)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("zi_rank%d" % rank if world > 1 else "zi", zq)], DUMP_BYTES // world)
     t = torch.tensor([wall, ev], dtype=torch.float64, device=dev)
     if dist_on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -258,7 +305,7 @@ def bench_config3(args, ctx, info, dev, world, rank, barrier, dist, dist_on):
                          "traffic_note": measured_traffic_config3(nq)[1],
                          "kernel": "interp2_kernel",
                          "kernel_ms": ks * 1e3, "algorithmic_bytes_per_launch": alg},
-            "cpu_baseline": None if args.no_cpu_baseline else cpu_baseline_config3(n3, nq),
+            "cpu_baseline": cpu_baseline_config3(n3, nq) if args.cpu_baseline else None,
             "device": info["name"]}), flush=True)
     if dist_on:
         dist.barrier()
@@ -332,6 +379,9 @@ def bench_group(args):
         tm.stop()
     grp.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("yi_shard%d" % r, y) for r, y in enumerate(yq)] +
+                     [("yi_gathered%d" % r, f) for r, f in enumerate(full or [])])
     ev = max(tm.elapsed_ms() for tm in timers) * 1e-3
     for tm in timers:
         tm.close()
@@ -356,7 +406,7 @@ def bench_group(args):
                      "kernel": "per device: the kernel mi_interp1_f64_dev picks for its shard",
                      "kernel_ms": ks * 1e3, "algorithmic_bytes_per_launch": alg,
                      "note": "slowest device's HIP-event time per step (events on each member's own stream)"},
-        "cpu_baseline": None if args.no_cpu_baseline else cpu_baseline(X, Y, nq, sample=100_000_000 if n == 1 else 20_000_000),
+        "cpu_baseline": cpu_baseline(X, Y, nq, sample=100_000_000 if n == 1 else 20_000_000) if args.cpu_baseline else None,
         "device": info["name"]}), flush=True)
     tab.close()
     grp.close()
@@ -442,6 +492,8 @@ def main():
     torch.cuda.synchronize()
 
     wall, ev = timed_loop(ctx, lambda: grid.interp(xq, out=yq), args.steps, args.warmup, barrier)
+    if args.dump_outputs:       # here: the secondary measurements below reuse yq as their output buffer
+        dump_outputs(args.dump_outputs, [("yi_rank%d" % rank if world > 1 else "yi", yq)], DUMP_BYTES // world)
     t = torch.tensor([wall, ev], dtype=torch.float64, device=dev)
     if dist_on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -500,7 +552,7 @@ def main():
                                          % (l2["gpu_clock_hz"] * 1e-9, l2.get("tcc_busy_frac") or float("nan")))
 
     extra = {}
-    if rank == 0 and not args.no_extra:
+    if rank == 0 and args.extra:
         reps = max(3, min(args.steps, 10))
 
         def quick(fn):
@@ -584,7 +636,7 @@ def main():
             "note": "opt-in mi_edm_params.dedup_identical: one realisation evolved, events replicated to all rows; "
                     "outputs bit-identical to the full evolution (tests/test_edm_gpu.py); only valid for sigma = 0"}
         edm.close()
-    if strong and dist_on and args.dist_backend == "nccl":
+    if args.full and strong and dist_on and args.dist_backend == "nccl":
         # "also report compute + all-gather": the result shards reassembled on every GPU by an RCCL
         # all-gather over xGMI inside the timed loop (ragged shards are padded to the largest)
         from armadillocudalinearinterpolation_amd import sharding as _sh
@@ -607,7 +659,7 @@ def main():
         del pad, full
     else:
         extra_strong = None
-    if dist_on and not args.no_extra and args.dist_backend == "nccl" and not strong:
+    if dist_on and args.extra and args.dist_backend == "nccl" and not strong:
         full = torch.empty(world * nq, dtype=torch.float64, device=dev)
         dist.all_gather_into_tensor(full, yq)
         torch.cuda.synchronize()
@@ -619,7 +671,7 @@ def main():
         extra["allgather_ms"] = (time.perf_counter() - t) * 1e3
         extra["allgather_note"] = "RCCL all-gather of %d x 8e8 B result shards, outside the timed region" % world
         del full
-    if dist_on and world > 1:
+    if args.full and dist_on and world > 1:
         # a reader of ONE file should be able to form the 1 -> N ratio: after the timed region rank 0 repeats the very same
         # step alone (the other ranks wait at the barrier below, their GPUs idle) -- the N = 1 time of this shard size
         torch.cuda.synchronize()
@@ -631,10 +683,11 @@ def main():
                                           "ms_per_step / n1_reference_ms is the slow-down of one shard when all %d GPUs run"
                                           % (nq, args.steps, world - 1, world))
     if rank == 0:
-        # the CPU baseline beside EVERY line (north_star: "reported at 1, 2, 4 and 8 GPUs alongside that CPU baseline"): the
-        # whole 1e8-query set at N = 1, a 2e7-query sample at N > 1 (the other ranks wait at the closing barrier meanwhile)
-        result["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(
-            X, Y, nq, sample=100_000_000 if world == 1 else 20_000_000, queries=args.queries)
+        # --full: the CPU baseline beside every line (north_star: "reported at 1, 2, 4 and 8 GPUs alongside that CPU
+        # baseline"): the whole 1e8-query set at N = 1, a 2e7-query sample at N > 1 (the other ranks wait at the closing
+        # barrier meanwhile)
+        result["cpu_baseline"] = cpu_baseline(
+            X, Y, nq, sample=100_000_000 if world == 1 else 20_000_000, queries=args.queries) if args.cpu_baseline else None
         result["extra"] = extra
         if extra_strong:
             result["strong_scaling"] = extra_strong

@@ -9,7 +9,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 cd "$REPO"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/stats.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > "$OUT/stats.log" 2>&1
 echo "rc=$?"
 ST=$(find "$OUT/stats" -name "*kernel_stats.csv" | head -1)
 grep -E "anonymous namespace|Name" "$ST" | cut -c1-220
