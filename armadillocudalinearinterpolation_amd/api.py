@@ -485,17 +485,7 @@ class EventDrivenMap:
 
     def debug_read(self):
         """Stage outputs of the last ComputeF (the reference's Save* taps, EventDrivenMap.cu:406-503)."""
-        S, R, N = int(self.params.n_spikes), int(self.params.n_real), int(self.params.n_grid)
-        out = {
-            "v": np.empty(N, np.float32), "s": np.empty(N, np.float32), "w": np.empty(N, np.float32),
-            "t0": np.empty(S * R, np.float32), "i0": np.empty(S * R, np.uint16),
-            "t1": np.empty(S * R, np.float32), "i1": np.empty(S * R, np.uint16),
-            "accept": np.empty(R, np.uint32), "restricted": np.empty(S * R, np.float32),
-            "seed_ind": np.empty(S, np.uint16),
-        }
-        order = ["v", "s", "w", "t0", "i0", "t1", "i1", "accept", "restricted", "seed_ind"]
-        check(self._L.mi_edm_debug_read(self._h, *[_ptr(out[k]) for k in order]), self._ctx._h)
-        return out
+        return _edm_debug_read(self._L, self._h, self.params, self._ctx._h)
 
     def debug_counters(self):
         """Decision-coverage taps of the last ComputeF (mi_edm_debug_counters: one more, tapped, evolve)."""
@@ -523,6 +513,21 @@ class EventDrivenMap:
             self.close()
         except Exception:
             pass
+
+
+def _edm_debug_read(L, h, params, ctx_h=None):
+    """mi_edm_debug_read of handle h, whose current parameters are params (n_spikes, n_real and n_grid size the taps)."""
+    S, R, N = int(params.n_spikes), int(params.n_real), int(params.n_grid)
+    out = {
+        "v": np.empty(N, np.float32), "s": np.empty(N, np.float32), "w": np.empty(N, np.float32),
+        "t0": np.empty(S * R, np.float32), "i0": np.empty(S * R, np.uint16),
+        "t1": np.empty(S * R, np.float32), "i1": np.empty(S * R, np.uint16),
+        "accept": np.empty(R, np.uint32), "restricted": np.empty(S * R, np.float32),
+        "seed_ind": np.empty(S, np.uint16),
+    }
+    order = ["v", "s", "w", "t0", "i0", "t1", "i1", "accept", "restricted", "seed_ind"]
+    check(L.mi_edm_debug_read(h, *[_ptr(out[k]) for k in order]), ctx_h)
+    return out
 
 
 # ---- several GPUs of one node, one host process (mi_group_*) ---------------------------------------------------
@@ -720,6 +725,18 @@ class GroupEventDrivenMap:
         lo, hi = C.c_size_t(0), C.c_size_t(0)
         check(self._L.mi_group_edm_shard_bounds(self._h, int(rank), C.byref(lo), C.byref(hi)))
         return lo.value, hi.value
+
+    def shard_debug_read(self, rank):
+        """Stage taps of the last ComputeF on shard `rank` (mi_group_edm_shard + mi_edm_debug_read): its realisations
+        [lo, hi) of shard_bounds(rank), laid out [spike][realisation of the shard]."""
+        h = self._L.mi_group_edm_shard(self._h, int(rank))
+        if not h:
+            raise ValueError("no shard %r in this group" % (rank,))
+        lo, hi = self.shard_bounds(rank)
+        par = EdmParams()
+        C.memmove(C.byref(par), C.byref(self.params), C.sizeof(EdmParams))
+        par.n_real = hi - lo
+        return _edm_debug_read(self._L, C.c_void_p(h), par)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -6,6 +6,7 @@ cpu_baseline leg of bench.py.  The product package never imports this module.
 import ctypes as C
 import os
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -321,3 +322,36 @@ def edm_compute_f(p, Z, seed_ind=None, nthreads=1, debug=True, counters=None, va
         raise ValueError("orc_edm_compute_f failed (%d)" % rc)
     dbg["seed_ind"] = ind
     return f, dbg
+
+
+def edm_realisation_taps(p, Z, reals, nthreads=1, block=32):
+    """Per-realisation taps of the launch p describes, for the realisations `reals` only (indices into the launch).
+    The oracle runs on contiguous blocks of them ([lo, hi) with n_real = hi - lo and real_offset = p.real_offset + lo:
+    the beta draw is keyed by the global realisation index, so a block equals that slice of the whole launch),
+    `nthreads` blocks at a time.  Returns {"reals": sorted unique indices, "t0", "i0", "t1", "i1": [n_spikes, len(reals)],
+    "accept": [len(reals)]}."""
+    reals = np.unique(np.asarray(reals, dtype=np.int64))
+    assert reals.size and reals[0] >= 0 and reals[-1] < p.n_real
+    runs, lo = [], 0
+    for k in range(1, reals.size + 1):                     # contiguous runs, cut into blocks of at most `block`
+        if k == reals.size or reals[k] != reals[k - 1] + 1 or k - lo == block:
+            runs.append((lo, k))
+            lo = k
+
+    def one(run):
+        q = EdmParams()
+        C.memmove(C.byref(q), C.byref(p), C.sizeof(EdmParams))
+        q.n_real = run[1] - run[0]
+        q.real_offset = int(p.real_offset) + int(reals[run[0]])
+        return edm_compute_f(q, Z, nthreads=1)[1]
+
+    S = int(p.n_spikes)
+    out = {"reals": reals, "accept": np.empty(reals.size, np.uint32)}
+    for k, dt in (("t0", np.float32), ("i0", np.uint16), ("t1", np.float32), ("i1", np.uint16)):
+        out[k] = np.empty((S, reals.size), dt)
+    with ThreadPoolExecutor(max(1, int(nthreads))) as pool:     # ctypes releases the GIL during the oracle call
+        for (a, b), d in zip(runs, pool.map(one, runs)):
+            for k in ("t0", "i0", "t1", "i1"):
+                out[k][:, a:b] = d[k].reshape(S, b - a)
+            out["accept"][a:b] = d["accept"]
+    return out

@@ -361,6 +361,14 @@ def test_dedup_identical_is_bit_identical_to_full_evolution(mi_ctx):
     _, f_dd, p_dd, d_dd = _run(mi_ctx, n_grid=512, n_real=3000, beta_stddev=0.3, dedup_identical=1)
     assert np.array_equal(f_full, f_dd) and np.array_equal(p_full, p_dd)
     assert np.array_equal(d_full["t0"], d_dd["t0"]) and not np.all(d_dd["t0"].reshape(3, 3000) == d_dd["t0"].reshape(3, 3000)[:, :1])
+    # ... and both are the oracle's realisations, not merely each other: both ends, a stretch in the middle, 96 at random
+    reals = np.concatenate([np.arange(16), np.arange(1496, 1512), np.arange(2984, 3000),
+                            np.random.default_rng(3000).choice(3000, 96, replace=False)])
+    o = oracle.edm_realisation_taps(oracle.edm_default_params(n_grid=512, n_real=3000, beta_stddev=0.3), Z_DRIVER, reals,
+                                    nthreads=8)
+    for k in ("t0", "i0", "t1", "i1"):
+        assert np.array_equal(d_dd[k].reshape(3, 3000)[:, o["reals"]], o[k], equal_nan=True), k
+    assert np.array_equal(d_dd["accept"][o["reals"]], o["accept"])
 
 
 def test_concurrent_evaluations_equal_sequential_ones(mi_ctx):
