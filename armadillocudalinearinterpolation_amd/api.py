@@ -287,6 +287,31 @@ class Grid2:
                                           float(extrap)), self._ctx._h)
         return out
 
+    def interp_grid(self, xi, yi, out=None, extrap=math.nan):
+        """arma::interp2's gridded output: ZI[i, j] = Z at (xi[j], yi[i]), a (nyi, nxi) tensor stored column-major (the
+        .T view of a contiguous (nxi, nyi) buffer).  xi, yi: contiguous float64 CUDA tensors (any order); out: that
+        contiguous (nxi, nyi) float64 buffer.  Asynchronous on the context's stream."""
+        torch = _torch()
+        for t in (xi, yi):
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+                raise ValueError("query axes must be contiguous float64 CUDA tensors")
+        nxi, nyi = xi.numel(), yi.numel()
+        if out is None:
+            out = torch.empty((nxi, nyi), dtype=torch.float64, device=xi.device)
+        elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (nxi, nyi)):
+            raise ValueError("out must be a contiguous float64 CUDA tensor of shape (len(xi), len(yi))")
+        check(self._L.mi_interp2_grid_f64_dev(self._ctx._h, self._h, _ptr(xi), nxi, _ptr(yi), nyi, _ptr(out),
+                                              float(extrap)), self._ctx._h)
+        return out.T
+
+    def interp_grid_host(self, xi, yi, extrap=math.nan):
+        """host form of interp_grid: numpy axes in, a Fortran-ordered (nyi, nxi) array out (synchronous)"""
+        xi, yi = _np64(xi), _np64(yi)
+        out = np.empty((xi.size, yi.size))
+        check(self._L.mi_interp2_grid_f64_host(self._ctx._h, self._h, _ptr(xi), xi.size, _ptr(yi), yi.size, _ptr(out),
+                                               float(extrap)), self._ctx._h)
+        return out.T
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.mi_grid2_destroy(self._h)
@@ -672,6 +697,14 @@ class GroupGrid2:
         out = np.empty_like(xq)
         check(self._L.mi_group_interp2_f64_host(self._g._h, self._h, _ptr(xq), _ptr(yq), _ptr(out), xq.size, float(extrap)))
         return out
+
+    def interp_grid_host(self, xi, yi, extrap=math.nan):
+        """gridded form (Grid2.interp_grid_host): the columns are sharded over the group's devices, yi replicated"""
+        xi, yi = _np64(xi), _np64(yi)
+        out = np.empty((xi.size, yi.size))
+        check(self._L.mi_group_interp2_grid_f64_host(self._g._h, self._h, _ptr(xi), xi.size, _ptr(yi), yi.size, _ptr(out),
+                                                     float(extrap)))
+        return out.T
 
     def interp_dev(self, xq_shards, yq_shards, extrap=math.nan, gather=False):
         """device-resident shards (one pair of float64 tensors per group member, equal sizes)"""

@@ -18,9 +18,10 @@ struct mi_ctx {
     size_t hbm_bytes = 0;
     char name[128] = {0};
     mutable char err[512] = {0};
-    // scratch for host-convenience entry points (grown on demand, never shrunk)
-    void* scratch[3] = {nullptr, nullptr, nullptr};
-    size_t scratch_bytes[3] = {0, 0, 0};
+    // scratch grown on demand, never shrunk: slots 0-2 for host-convenience entry points, slot 3 for the per-axis
+    // records of the gridded bilinear call (mi_interp2_grid_f64_dev)
+    void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[4] = {0, 0, 0, 0};
     // fixed workspace for cross-workgroup reductions, allocated at creation so
     // that device entry points never allocate
     void* reduce_ws = nullptr;

@@ -169,7 +169,7 @@ mi_status mi_ctx_destroy(mi_ctx* ctx)
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->owned_stream && ctx->owned_stream != ctx->stream) (void)hipStreamSynchronize(ctx->owned_stream);
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < 4; ++i)
         if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     if (ctx->reduce_ws) (void)hipFree(ctx->reduce_ws);
     if (ctx->owned_stream) (void)hipStreamDestroy(ctx->owned_stream);

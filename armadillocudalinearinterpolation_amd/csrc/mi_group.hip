@@ -549,6 +549,55 @@ mi_status mi_group_interp2_f64_host(mi_group* g, const mi_group_grid2* t, const 
     return MI_OK;
 }
 
+mi_status mi_group_interp2_grid_f64_host(mi_group* g, const mi_group_grid2* t, const double* xi, size_t nxi, const double* yi,
+                                         size_t nyi, double* zi, double extrap)
+{
+    MI_REQUIRE(nullptr, g && t, "mi_group_interp2_grid_f64_host: NULL argument");
+    MI_REQUIRE(nullptr, t->g == g && t->grid.size() == g->ctx.size(), "mi_group_interp2_grid_f64_host: the table belongs to another group");
+    if (nxi == 0 || nyi == 0) return MI_OK;
+    MI_REQUIRE(nullptr, xi && yi && zi, "mi_group_interp2_grid_f64_host: NULL query/result pointer");
+    MI_REQUIRE(nullptr, nxi <= SIZE_MAX / sizeof(double) / nyi, "mi_group_interp2_grid_f64_host: nxi=%zu x nyi=%zu too large", nxi, nyi);
+    const int P = (int)g->ctx.size();
+    const bool pin_x = mi::pin_host(xi, nxi * sizeof(double)), pin_y = mi::pin_host(yi, nyi * sizeof(double)),
+               pin_z = mi::pin_host(zi, nxi * nyi * sizeof(double));
+    mi_status st = MI_OK;
+    hipError_t herr = hipSuccess;
+    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
+        size_t lo, hi;
+        mi_shard_bounds(nxi, r, P, &lo, &hi);    // columns: one contiguous slice of the column-major zi
+        if (hi == lo) continue;
+        mi_ctx* c = g->ctx[r];
+        herr = hipSetDevice(g->dev[r]);
+        if (herr != hipSuccess) break;
+        const size_t m = hi - lo;
+        st = mi::ensure_scratch(c, 0, m * sizeof(double));
+        if (st == MI_OK) st = mi::ensure_scratch(c, 1, nyi * sizeof(double));
+        if (st == MI_OK) st = mi::ensure_scratch(c, 2, m * nyi * sizeof(double));
+        if (st != MI_OK) break;
+        herr = hipMemcpyAsync(c->scratch[0], xi + lo, m * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (herr != hipSuccess) break;
+        herr = hipMemcpyAsync(c->scratch[1], yi, nyi * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (herr != hipSuccess) break;
+        st = mi_interp2_grid_f64_dev(c, t->grid[r], (const double*)c->scratch[0], m, (const double*)c->scratch[1], nyi,
+                                     (double*)c->scratch[2], extrap);
+        if (st != MI_OK) break;
+        herr = hipMemcpyAsync(zi + lo * nyi, c->scratch[2], m * nyi * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    }
+    hipError_t esync = hipSuccess;
+    for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
+        (void)hipSetDevice(g->dev[r]);
+        const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
+        if (e != hipSuccess && esync == hipSuccess) esync = e;
+    }
+    if (pin_x) mi::unpin_host(xi);
+    if (pin_y) mi::unpin_host(yi);
+    if (pin_z) mi::unpin_host(zi);
+    if (st != MI_OK) return st;
+    if (herr != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp2_grid_f64_host: copy failed: %s", hipGetErrorString(herr));
+    if (esync != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp2_grid_f64_host: %s", hipGetErrorString(esync));
+    return MI_OK;
+}
+
 // ---- EventDrivenMap -----------------------------------------------------------------------------------------------
 
 static mi_status edm_shard_params(const mi_group_edm* e, int r, mi_edm_params* p)

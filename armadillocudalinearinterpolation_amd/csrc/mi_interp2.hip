@@ -11,127 +11,16 @@
 //   quad cells    element (l,c) = {Z(l,c), Z(l,rx), Z(ry,c), Z(ry,rx)}, 32 B, 32-B
 //                 aligned = exactly one 64-B sector per query; 4x the input bytes
 // HBM3E capacity (288 GB) is what makes spending 2-4x on a 128 MiB table sensible.
-// Compiled with -ffp-contract=off (every product/sum rounds separately).
+// Compiled with -ffp-contract=off (every product/sum rounds separately).  Table handle, layouts' element types and the
+// shared arithmetic: mi_interp2_eval.hpp.
 #include <algorithm>
 #include <cmath>
 #include <new>
 #include <vector>
 
-#include "mi_common.hpp"
-
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-struct AxisDev {
-    const double* nodes;   // explicit axis (null when implicit)
-    int n;
-    int use_guess;         // explicit: analytic guess + walk (1) or binary search (0)
-    double xmin, xmax, scale;
-    double x0, dx;         // implicit: node_i = fma(i, dx, x0)
-};
-
-typedef double d2v __attribute__((ext_vector_type(2)));
-
-struct G2Dev {
-    AxisDev ax, ay;
-    const d2v* zp;         // (ny*nx + 1) column pairs {Z(l,c), Z(l,c+1)}, index l + c*ny
-    int quads;             // 1: zp holds 2*ny*nx d2v: cell (l,c) = {Z(l,c), Z(l,rx)}, {Z(ry,c), Z(ry,rx)} (32 B)
-};
-
-struct mi_grid2 {
-    mi_ctx* ctx;
-    int device;            // copied at creation: destroy must not dereference a context that may be gone
-    void* dev_x;
-    void* dev_y;
-    void* dev_z;
-    G2Dev d;
-    size_t table_bytes = 0;
-};
+#include "mi_interp2_eval.hpp"
 
 namespace mi_interp2 {
-
-constexpr int kBlock = 256;
-constexpr int kMaxWalk = 4;
-
-// IMPL: the axis is known to be implicit (uniform) at compile time -- no node loads, no search branches; the arithmetic
-// is the one the general form takes for such an axis
-template <bool IMPL = false>
-__device__ __forceinline__ double axis_node(const AxisDev& a, int i)
-{
-    if constexpr (IMPL) return fma((double)i, a.dx, a.x0);
-    return a.nodes ? a.nodes[i] : fma((double)i, a.dx, a.x0);
-}
-
-// largest l with node_l <= q (q inside [xmin, xmax])
-template <bool IMPL = false>
-__device__ __forceinline__ int axis_locate(const AxisDev& a, double q)
-{
-    if (!IMPL && a.nodes && !a.use_guess) {
-        int lo = 0, hi = a.n;
-        while (hi - lo > 1) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (a.nodes[mid] <= q) lo = mid; else hi = mid;
-        }
-        return lo;
-    }
-    int i = (int)((q - a.xmin) * a.scale);
-    i = min(max(i, 0), a.n - 1);
-    while (i > 0 && axis_node<IMPL>(a, i) > q) --i;
-    while (i < a.n - 1 && axis_node<IMPL>(a, i + 1) <= q) ++i;
-    return i;
-}
-
-__device__ __forceinline__ double weight(double xa, double xb, double q)
-{
-    const double a = q - xa, b = xb - q;
-    return (a > 0.0) ? a / (a + b) : 0.0;
-}
-
-// eval2 in three steps, so that a kernel can put the cell loads of several queries in flight together
-// (interp2_blocks_kernel); the direct kernel runs them back to back.  Same operations in the same order either way.
-struct Loc2 {
-    double sx, sy;       // the query, or the grid's origin for an out-of-range / NaN query (its result is replaced)
-    int lx, ly, rx, ry;
-    bool oor;
-    const d2v* cell;     // two consecutive 16-B elements: {Z(ly,lx), Z(ly,rx)}, then the next row's pair / the quad's second half
-};
-
-template <bool IMPL = false>
-__device__ __forceinline__ Loc2 locate2(const G2Dev& g, double qx, double qy)
-{
-    Loc2 L;
-    L.oor = !(qx >= g.ax.xmin && qx <= g.ax.xmax && qy >= g.ay.xmin && qy <= g.ay.xmax);
-    L.sx = L.oor ? g.ax.xmin : qx;
-    L.sy = L.oor ? g.ay.xmin : qy;
-    L.lx = axis_locate<IMPL>(g.ax, L.sx);
-    L.ly = axis_locate<IMPL>(g.ay, L.sy);
-    L.rx = min(L.lx + 1, g.ax.n - 1);
-    L.ry = min(L.ly + 1, g.ay.n - 1);
-    const size_t k = (size_t)L.lx * (size_t)g.ay.n + L.ly;
-    L.cell = g.quads ? g.zp + 2 * k : g.zp + k;
-    return L;
-}
-
-// lo = cell[0] = {Z(ly,lx), Z(ly,rx)}; hi = cell[1]: pairs: next row (padding past the last); quads: {Z(ry,lx), Z(ry,rx)}
-template <bool IMPL = false>
-__device__ __forceinline__ double blend2(const G2Dev& g, const Loc2& L, d2v lo, d2v hi, double qx, double qy, double extrap)
-{
-    const double wx = weight(axis_node<IMPL>(g.ax, L.lx), axis_node<IMPL>(g.ax, L.rx), L.sx);
-    const double wy = weight(axis_node<IMPL>(g.ay, L.ly), axis_node<IMPL>(g.ay, L.ry), L.sy);
-    const double z01 = (L.ry != L.ly) ? hi.x : lo.x;
-    const double z11 = (L.ry != L.ly) ? hi.y : lo.y;
-    const double c0 = (1.0 - wy) * lo.x + wy * z01;
-    const double c1 = (1.0 - wy) * lo.y + wy * z11;
-    const double r = (1.0 - wx) * c0 + wx * c1;
-    if (L.oor) return (qx != qx || qy != qy) ? __builtin_nan("") : extrap;
-    return r;
-}
-
-__device__ __forceinline__ double eval2(const G2Dev& g, double qx, double qy, double extrap)
-{
-    const Loc2 L = locate2(g, qx, qy);
-    const d2v lo = L.cell[0], hi = L.cell[1];
-    return blend2(g, L, lo, hi, qx, qy, extrap);
-}
 
 // One 16-B vector of each coordinate stream (two queries) per lane, one workgroup per 256 vectors: the
 // launch shape that streams fastest on MI355X (see mi_interp1.hip).

@@ -4,7 +4,9 @@
 //
 //   mi355::interp1(X, Y, XI, YI)            == arma::interp1(X, Y, XI, YI, "linear")
 //   mi355::Interp1Table tab(X, Y); tab(XI, YI)   table resident in HBM across calls
-//   mi355::interp2(X, Y, Z, XI, YI, ZI)     scattered bilinear, Z = arma::mat(Y.n_elem, X.n_elem)
+//   mi355::interp2(X, Y, Z, XI, YI, ZI)     ZI an arma::mat: == arma::interp2(X, Y, Z, XI, YI, ZI, "linear", extrap),
+//                                           ZI = YI.n_elem x XI.n_elem; Z = arma::mat(Y.n_elem, X.n_elem)
+//                                           ZI an arma::vec: scattered extension, one result per (XI[k], YI[k]) pair
 //   mi355::restrict_to_horizon(...)         RestrictKernel (EventDrivenMap.cu:769-785) on host vectors
 //   mi355::DeviceGroup grp(8); mi355::GroupInterp1Table tab(grp, X, Y); tab(XI, YI)
 //                                           the same call with the queries sharded over the GPUs of the node
@@ -98,8 +100,9 @@ inline void interp1(const arma::vec& X, const arma::vec& Y, const arma::vec& XI,
           dev.get(), "mi_interp1_f64");
 }
 
-// Scattered bilinear interpolation: ZI[k] = Z(YI[k], XI[k]); Z is Y.n_elem x X.n_elem (rows follow Y), the
-// layout arma::interp2 uses for its Z argument.  One result per query PAIR (not arma::interp2's gridded output).
+// Scattered bilinear interpolation (an extension, not an Armadillo call): ZI[k] = Z(YI[k], XI[k]); Z is
+// Y.n_elem x X.n_elem (rows follow Y), the layout arma::interp2 uses for its Z argument.  One result per query PAIR.
+// With the real Armadillo an arma::vec ZI binds here (exact match) rather than to the arma::mat overload below.
 inline void interp2(const arma::vec& X, const arma::vec& Y, const arma::mat& Z, const arma::vec& XI,
                     const arma::vec& YI, arma::vec& ZI,
                     double extrap_val = std::numeric_limits<double>::quiet_NaN(), Device& dev = Device::instance())
@@ -113,6 +116,23 @@ inline void interp2(const arma::vec& X, const arma::vec& Y, const arma::mat& Z, 
     mi_status st = mi_interp2_f64_host(dev.get(), g, XI.memptr(), YI.memptr(), ZI.memptr(), XI.n_elem, extrap_val);
     mi_grid2_destroy(g);
     check(st, dev.get(), "mi_interp2_f64_host");
+}
+
+// arma::interp2(X, Y, Z, XI, YI, ZI, "linear", extrap_val): ZI = YI.n_elem x XI.n_elem, ZI(i, j) = Z at (XI[j], YI[i]),
+// bit-identical to the scattered overload on that pair.
+inline void interp2(const arma::vec& X, const arma::vec& Y, const arma::mat& Z, const arma::vec& XI,
+                    const arma::vec& YI, arma::mat& ZI,
+                    double extrap_val = std::numeric_limits<double>::quiet_NaN(), Device& dev = Device::instance())
+{
+    if (Z.n_rows != Y.n_elem || Z.n_cols != X.n_elem) throw std::invalid_argument("interp2(): Z must be Y.n_elem x X.n_elem");
+    mi_grid2* g = nullptr;
+    check(mi_grid2_create(dev.get(), X.memptr(), X.n_elem, Y.memptr(), Y.n_elem, Z.memptr(), 0u, &g), dev.get(),
+          "mi_grid2_create");
+    ZI.set_size(YI.n_elem, XI.n_elem);
+    mi_status st = mi_interp2_grid_f64_host(dev.get(), g, XI.memptr(), XI.n_elem, YI.memptr(), YI.n_elem, ZI.memptr(),
+                                            extrap_val);
+    mi_grid2_destroy(g);
+    check(st, dev.get(), "mi_interp2_grid_f64_host");
 }
 
 // RestrictKernel (EventDrivenMap.cu:769-785) on host vectors: position at t = final_time from the last event
@@ -171,8 +191,9 @@ class GroupInterp1Table {
     mi_group_grid1* t_;
 };
 
-// Scattered bilinear interpolation (BASELINE config 3) over the group: Z = arma::mat(Y.n_elem, X.n_elem) replicated, the
-// query pairs sharded; one result per pair, as mi355::interp2.
+// Bilinear interpolation over the group: Z = arma::mat(Y.n_elem, X.n_elem) replicated.  ZI an arma::vec: scattered
+// (BASELINE config 3), the query pairs sharded, one result per pair; ZI an arma::mat: arma::interp2's gridded output,
+// the columns of ZI sharded -- both as the mi355::interp2 overloads.
 class GroupInterp2Table {
   public:
     GroupInterp2Table(DeviceGroup& grp, const arma::vec& X, const arma::vec& Y, const arma::mat& Z) : grp_(grp), t_(nullptr)
@@ -191,6 +212,14 @@ class GroupInterp2Table {
         ZI.set_size(XI.n_elem);
         check(mi_group_interp2_f64_host(grp_.get(), t_, XI.memptr(), YI.memptr(), ZI.memptr(), XI.n_elem, extrap_val), nullptr,
               "mi_group_interp2_f64_host");
+    }
+    void operator()(const arma::vec& XI, const arma::vec& YI, arma::mat& ZI,
+                    double extrap_val = std::numeric_limits<double>::quiet_NaN()) const
+    {
+        ZI.set_size(YI.n_elem, XI.n_elem);
+        check(mi_group_interp2_grid_f64_host(grp_.get(), t_, XI.memptr(), XI.n_elem, YI.memptr(), YI.n_elem, ZI.memptr(),
+                                             extrap_val),
+              nullptr, "mi_group_interp2_grid_f64_host");
     }
 
   private:

@@ -49,7 +49,9 @@ extern "C" {
  *                was bit-identical and 24 % slower than the direct kernel; it is a recorded experiment now,
  *                scripts/exp_interp2_ordered.hpp, profiles/r03_config3_ordered_*); mi_grid2_info reports the table size only;
  *              + mi_edm_set_kernel_choice (replaces two environment hooks), mi_edm_debug_counters,
- *                mi_group_set_gather_chunks */
+ *                mi_group_set_gather_chunks;
+ *              additive in 4: mi_interp2_grid_f64_dev, mi_interp2_grid_f64_host, mi_group_interp2_grid_f64_host (the
+ *                gridded arma::interp2 output) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -173,6 +175,15 @@ mi_status mi_interp2_f64_dev(mi_ctx* ctx, const mi_grid2* g, const double* xq_de
                              const double* yq_dev, double* zq_dev, size_t nq, double extrap_val);
 mi_status mi_interp2_f64_host(mi_ctx* ctx, const mi_grid2* g, const double* xq, const double* yq,
                               double* zq, size_t nq, double extrap_val);
+/* Gridded form, arma::interp2(X, Y, Z, XI, YI, ZI): zi is column-major nyi x nxi, i.e.
+ * arma::mat(nyi, nxi).memptr(), zi[i + j*nyi] = Z at (xi[j], yi[i]), bit-identical to mi_interp2_f64_dev on that
+ * pair.  xi, yi need not be sorted.  Each coordinate is located once per call (records in a workspace the context
+ * owns, grown on demand); the output is written once.  _dev: device pointers, 8-B aligned, asynchronous on the
+ * context's stream; nxi == 0 or nyi == 0 is MI_OK with nothing launched.  _host: host pointers, synchronous. */
+mi_status mi_interp2_grid_f64_dev(mi_ctx* ctx, const mi_grid2* g, const double* xi_dev, size_t nxi,
+                                  const double* yi_dev, size_t nyi, double* zi_dev, double extrap_val);
+mi_status mi_interp2_grid_f64_host(mi_ctx* ctx, const mi_grid2* g, const double* xi, size_t nxi,
+                                   const double* yi, size_t nyi, double* zi, double extrap_val);
 
 /* ---- the reference's own interpolation ----------------------------------
  * Replaces RestrictKernel (EventDrivenMap.cu:769-785, launch :205-206):
@@ -383,6 +394,10 @@ mi_status mi_group_interp2_f64_host(mi_group* g, const mi_group_grid2* t, const 
 mi_status mi_group_interp2_f64_dev(mi_group* g, const mi_group_grid2* t, const double* const* xq_dev,
                                    const double* const* yq_dev, double* const* zq_dev, size_t nq_per_shard,
                                    double extrap_val, double* const* gathered_dev);
+/* Gridded form over the group (mi_interp2_grid_f64_host): member r computes the columns [lo, hi) =
+ * mi_shard_bounds(nxi, r, P), one contiguous slice of the column-major zi; yi is replicated.  Synchronous. */
+mi_status mi_group_interp2_grid_f64_host(mi_group* g, const mi_group_grid2* t, const double* xi, size_t nxi,
+                                         const double* yi, size_t nyi, double* zi, double extrap_val);
 
 /* EventDrivenMap with the realisations sharded over the group: p->n_real is the TOTAL (>= group size); shard r evolves
  * realisations [lo_r, hi_r) = mi_shard_bounds(n_real, r, P) with real_offset = p->real_offset + lo_r, so the per-neuron
