@@ -324,6 +324,102 @@ class Grid2:
             pass
 
 
+class Axis1:
+    """Validated, device-resident 1-D axis (mi_axis1) for interp1 over the columns of a matrix: one X, many Y.
+
+    Layout, as arma::mat: Y is (n, B) with one profile per COLUMN, stored column-major -- element (i, c) at
+    i + c*ld -- and so is the (nxi, B) result.  In torch / numpy terms that is the .T view of a C-contiguous (B, n)
+    buffer (a realisation per row of the buffer); a view with a row stride ld > n (buffer[:, :n].T) is taken as it is.
+    X is used as given ("*linear" contract): strictly increasing and finite, else MiError (MI_ERR_GRID)."""
+
+    def __init__(self, ctx, handle, n):
+        self._ctx, self._h, self._L, self.n = ctx, handle, ctx._L, int(n)
+        if hasattr(ctx, "_children"):
+            ctx._children.add(self)
+
+    @classmethod
+    def from_nodes(cls, ctx, x):
+        x = _np64(x)
+        h = C.c_void_p()
+        check(ctx._L.mi_axis1_create(ctx._h, _ptr(x), x.size, 0, C.byref(h)), ctx._h)
+        return cls(ctx, h, x.size)
+
+    @classmethod
+    def from_device_nodes(cls, ctx, x):
+        """nodes already resident on the device (a contiguous float64 CUDA tensor)"""
+        h = C.c_void_p()
+        check(ctx._L.mi_axis1_create(ctx._h, _ptr(x), x.numel(), MI_GRID_DEVICE_PTRS, C.byref(h)), ctx._h)
+        return cls(ctx, h, x.numel())
+
+    @classmethod
+    def uniform(cls, ctx, x0, dx, n):
+        """implicit nodes X_i = fma(i, dx, x0)"""
+        h = C.c_void_p()
+        check(ctx._L.mi_axis1_create_uniform(ctx._h, float(x0), float(dx), int(n), C.byref(h)), ctx._h)
+        return cls(ctx, h, n)
+
+    @staticmethod
+    def _colmajor_view(a, rows, what):
+        """(leading dimension, columns) of a 2-D (rows, B) array or tensor stored column-major; strides in elements"""
+        shape = tuple(a.shape)
+        if len(shape) != 2 or shape[0] != rows:
+            raise ValueError("%s must have shape (%d, B)" % (what, rows))
+        st = a.stride() if hasattr(a, "stride") else tuple(s // a.itemsize for s in a.strides)
+        B = shape[1]
+        ld = st[1] if B > 1 else max(rows, 1)
+        if (rows > 1 and st[0] != 1) or ld < rows:
+            raise ValueError("%s must be column-major (the .T view of a contiguous (B, %d) buffer)" % (what, rows))
+        return ld, B
+
+    def interp_cols(self, Y, xi, out=None, extrap=math.nan):
+        """Y: (n, B) float64 CUDA tensor, column-major (see the class docstring); xi: contiguous float64 CUDA tensor of
+        nxi queries in any order; out: column-major (nxi, B) tensor (default: the .T view of a new contiguous (B, nxi)
+        buffer).  Returns the (nxi, B) result; asynchronous on the context's stream."""
+        torch = _torch()
+        if not (xi.is_cuda and xi.dtype == torch.float64 and xi.is_contiguous()):
+            raise ValueError("xi must be a contiguous float64 CUDA tensor")
+        if not (Y.is_cuda and Y.dtype == torch.float64):
+            raise ValueError("Y must be a float64 CUDA tensor")
+        ldy, B = self._colmajor_view(Y, self.n, "Y")
+        nxi = xi.numel()
+        if out is None:
+            out = torch.empty((B, nxi), dtype=torch.float64, device=Y.device).T
+        elif not (out.is_cuda and out.dtype == torch.float64):
+            raise ValueError("out must be a float64 CUDA tensor")
+        ldyi, Bo = self._colmajor_view(out, nxi, "out")
+        if Bo != B:
+            raise ValueError("out must have as many columns as Y")
+        check(self._L.mi_interp1_cols_f64_dev(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, B, _ptr(xi), nxi,
+                                              C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
+        return out
+
+    def interp_cols_host(self, Y, xi, extrap=math.nan):
+        """host form: Y a (n, B) numpy array (any layout; a column-major one is used in place), xi numpy queries;
+        returns a Fortran-ordered (nxi, B) array (synchronous)"""
+        xi = _np64(xi)
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[0] != self.n:
+            raise ValueError("Y must have shape (%d, B)" % self.n)
+        if not Y.flags["F_CONTIGUOUS"]:
+            Y = np.asfortranarray(Y)
+        B = Y.shape[1]
+        out = np.empty((B, xi.size)).T
+        check(self._L.mi_interp1_cols_f64_host(self._ctx._h, self._h, C.c_void_p(Y.ctypes.data), self.n, B, _ptr(xi), xi.size,
+                                               C.c_void_p(out.ctypes.data), xi.size, float(extrap)), self._ctx._h)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mi_axis1_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- the reference's own step: Restrict + masked mean (EventDrivenMap.cu:769-824) ----
 
 def restrict(ctx, t0, i0, t1, i1, final_time, half_length, ngrid, out=None):
@@ -624,6 +720,21 @@ class Group:
         check(self._L.mi_group_grid2_create(self._h, _ptr(x), x.size, _ptr(y), y.size, _ptr(zc),
                                             MI_GRID2_COMPACT if compact else 0, C.byref(t)))
         return GroupGrid2(self, t)
+
+    def interp_cols_host(self, X, Y, xi, extrap=math.nan):
+        """interp1 over the columns of Y (Axis1.interp_cols_host) with the columns sharded over the group's devices;
+        X (n nodes, used as given) and xi are replicated.  Y: (n, B) numpy array; returns a Fortran-ordered (nxi, B) array."""
+        X, xi = _np64(X), _np64(xi)
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[0] != X.size:
+            raise ValueError("Y must have shape (len(X), B)")
+        if not Y.flags["F_CONTIGUOUS"]:
+            Y = np.asfortranarray(Y)
+        B = Y.shape[1]
+        out = np.empty((B, xi.size)).T
+        check(self._L.mi_group_interp1_cols_f64_host(self._h, _ptr(X), X.size, C.c_void_p(Y.ctypes.data), X.size, B, _ptr(xi),
+                                                     xi.size, C.c_void_p(out.ctypes.data), xi.size, float(extrap)))
+        return out
 
     def edm(self, parameters, noReal, **overrides):
         return GroupEventDrivenMap(self, parameters, noReal, **overrides)

@@ -598,6 +598,76 @@ mi_status mi_group_interp2_grid_f64_host(mi_group* g, const mi_group_grid2* t, c
     return MI_OK;
 }
 
+// interp1 over the columns of a matrix (mi_cols1.hip), columns sharded: member r takes [lo, hi) = mi_shard_bounds(ncols, r, P).
+// X and XI are replicated; each member gets an axis of its own for the duration of the call.  Device copies are compact
+// (leading dimensions n and nxi): slot 0 XI, slot 1 the member's columns of Y, slot 2 its columns of YI.
+static hipError_t group_copy_cols(double* dst, size_t ld_dst, const double* src, size_t ld_src, size_t rows, size_t ncols,
+                                  hipMemcpyKind kind, hipStream_t stream)
+{
+    if (ld_dst == rows && ld_src == rows) return hipMemcpyAsync(dst, src, rows * ncols * sizeof(double), kind, stream);
+    return hipMemcpy2DAsync(dst, ld_dst * sizeof(double), src, ld_src * sizeof(double), rows * sizeof(double), ncols, kind, stream);
+}
+
+mi_status mi_group_interp1_cols_f64_host(mi_group* g, const double* x, size_t n, const double* y, size_t ldy, size_t ncols,
+                                         const double* xi, size_t nxi, double* yi, size_t ldyi, double extrap)
+{
+    MI_REQUIRE(nullptr, g && x, "mi_group_interp1_cols_f64_host: NULL argument");
+    const int P = (int)g->ctx.size();
+    // one axis per member: validates X (MI_ERR_GRID) whatever ncols and nxi are
+    std::vector<mi_axis1*> axis(P, nullptr);
+    mi_status st = MI_OK;
+    for (int r = 0; r < P && st == MI_OK; ++r) {
+        if (hipSetDevice(g->dev[r]) != hipSuccess) st = mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_cols_f64_host: hipSetDevice(%d) failed", g->dev[r]);
+        else st = mi_axis1_create(g->ctx[r], x, n, 0, &axis[r]);   // a failure's text is also the calling thread's last error
+    }
+    if (st == MI_OK && ncols != 0 && nxi != 0) {
+        if (!(y && xi && yi)) st = mi::fail(nullptr, MI_ERR_INVALID_ARG, "mi_group_interp1_cols_f64_host: NULL table/query/result pointer");
+        else if (ldy < n) st = mi::fail(nullptr, MI_ERR_INVALID_ARG, "mi_group_interp1_cols_f64_host: ldy=%zu is smaller than the axis (n=%zu)", ldy, n);
+        else if (ldyi < nxi) st = mi::fail(nullptr, MI_ERR_INVALID_ARG, "mi_group_interp1_cols_f64_host: ldyi=%zu is smaller than nxi=%zu", ldyi, nxi);
+        else if (ldy > SIZE_MAX / sizeof(double) / ncols || ldyi > SIZE_MAX / sizeof(double) / ncols)
+            st = mi::fail(nullptr, MI_ERR_INVALID_ARG, "mi_group_interp1_cols_f64_host: ncols=%zu x (ldy=%zu, ldyi=%zu) too large", ncols, ldy, ldyi);
+    }
+    if (st == MI_OK && ncols != 0 && nxi != 0) {
+        const bool pin_x = mi::pin_host(xi, nxi * sizeof(double)), pin_y = mi::pin_host(y, ((ncols - 1) * ldy + n) * sizeof(double)),
+                   pin_o = mi::pin_host(yi, ((ncols - 1) * ldyi + nxi) * sizeof(double));
+        hipError_t herr = hipSuccess;
+        for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
+            size_t lo, hi;
+            mi_shard_bounds(ncols, r, P, &lo, &hi);
+            if (hi == lo) continue;
+            mi_ctx* c = g->ctx[r];
+            herr = hipSetDevice(g->dev[r]);
+            if (herr != hipSuccess) break;
+            const size_t m = hi - lo;
+            st = mi::ensure_scratch(c, 0, nxi * sizeof(double));
+            if (st == MI_OK) st = mi::ensure_scratch(c, 1, m * n * sizeof(double));
+            if (st == MI_OK) st = mi::ensure_scratch(c, 2, m * nxi * sizeof(double));
+            if (st != MI_OK) break;
+            double *dxi = (double*)c->scratch[0], *dy = (double*)c->scratch[1], *dyi = (double*)c->scratch[2];
+            herr = hipMemcpyAsync(dxi, xi, nxi * sizeof(double), hipMemcpyHostToDevice, c->stream);
+            if (herr != hipSuccess) break;
+            herr = group_copy_cols(dy, n, y + lo * ldy, ldy, n, m, hipMemcpyHostToDevice, c->stream);
+            if (herr != hipSuccess) break;
+            st = mi_interp1_cols_f64_dev(c, axis[r], dy, n, m, dxi, nxi, dyi, nxi, extrap);
+            if (st != MI_OK) break;
+            herr = group_copy_cols(yi + lo * ldyi, ldyi, dyi, nxi, nxi, m, hipMemcpyDeviceToHost, c->stream);
+        }
+        hipError_t esync = hipSuccess;
+        for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
+            (void)hipSetDevice(g->dev[r]);
+            const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
+            if (e != hipSuccess && esync == hipSuccess) esync = e;
+        }
+        if (pin_x) mi::unpin_host(xi);
+        if (pin_y) mi::unpin_host(y);
+        if (pin_o) mi::unpin_host(yi);
+        if (st == MI_OK && herr != hipSuccess) st = mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_cols_f64_host: copy failed: %s", hipGetErrorString(herr));
+        if (st == MI_OK && esync != hipSuccess) st = mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_cols_f64_host: %s", hipGetErrorString(esync));
+    }
+    for (int r = 0; r < P; ++r) mi_axis1_destroy(axis[r]);
+    return st;
+}
+
 // ---- EventDrivenMap -----------------------------------------------------------------------------------------------
 
 static mi_status edm_shard_params(const mi_group_edm* e, int r, mi_edm_params* p)

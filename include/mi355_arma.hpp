@@ -4,6 +4,9 @@
 //
 //   mi355::interp1(X, Y, XI, YI)            == arma::interp1(X, Y, XI, YI, "linear")
 //   mi355::Interp1Table tab(X, Y); tab(XI, YI)   table resident in HBM across calls
+//   mi355::interp1(X, Y, XI, YI)            Y, YI arma::mat: interp1 on every column of Y (MATLAB's interp1 with a matrix
+//                                           Y), YI = XI.n_elem x Y.n_cols; X as given ("*linear": strictly increasing)
+//   mi355::Interp1Axis ax(X); ax(Y, XI, YI)      the axis resident across calls while Y changes
 //   mi355::interp2(X, Y, Z, XI, YI, ZI)     ZI an arma::mat: == arma::interp2(X, Y, Z, XI, YI, ZI, "linear", extrap),
 //                                           ZI = YI.n_elem x XI.n_elem; Z = arma::mat(Y.n_elem, X.n_elem)
 //                                           ZI an arma::vec: scattered extension, one result per (XI[k], YI[k]) pair
@@ -100,6 +103,49 @@ inline void interp1(const arma::vec& X, const arma::vec& Y, const arma::vec& XI,
           dev.get(), "mi_interp1_f64");
 }
 
+// interp1 over the columns of a matrix: YI(:, c) = arma::interp1(X, Y.col(c), XI, YI.col(c), "*linear", extrap_val) for
+// every column c, bit-identical to Interp1Table(X, Y.col(c), false) on XI.  The axis is validated and uploaded once and
+// reused while Y changes.  "*linear" contract: X is used as given and must be strictly increasing and finite (it is not
+// sorted or de-duplicated for the caller, which would mean permuting the rows of every Y); otherwise the call throws.
+class Interp1Axis {
+  public:
+    explicit Interp1Axis(const arma::vec& X, Device& dev = Device::instance()) : dev_(dev), a_(nullptr), n_(X.n_elem)
+    {
+        check(mi_axis1_create(dev_.get(), X.memptr(), X.n_elem, 0u, &a_), dev_.get(), "mi_axis1_create");
+    }
+    // nodes fma(i, dx, x0), i < n
+    Interp1Axis(double x0, double dx, size_t n, Device& dev = Device::instance()) : dev_(dev), a_(nullptr), n_(n)
+    {
+        check(mi_axis1_create_uniform(dev_.get(), x0, dx, n, &a_), dev_.get(), "mi_axis1_create_uniform");
+    }
+    ~Interp1Axis() { mi_axis1_destroy(a_); }
+    Interp1Axis(const Interp1Axis&) = delete;
+    Interp1Axis& operator=(const Interp1Axis&) = delete;
+
+    void operator()(const arma::mat& Y, const arma::vec& XI, arma::mat& YI,
+                    double extrap_val = std::numeric_limits<double>::quiet_NaN()) const
+    {
+        if (Y.n_rows != n_) throw std::invalid_argument("interp1(): Y must have X.n_elem rows");
+        YI.set_size(XI.n_elem, Y.n_cols);
+        check(mi_interp1_cols_f64_host(dev_.get(), a_, Y.memptr(), Y.n_rows, Y.n_cols, XI.memptr(), XI.n_elem, YI.memptr(),
+                                       XI.n_elem, extrap_val),
+              dev_.get(), "mi_interp1_cols_f64_host");
+    }
+
+  private:
+    Device& dev_;
+    mi_axis1* a_;
+    size_t n_;
+};
+
+// one-shot form: Y, YI matrices (the vector overload above is arma::interp1 itself)
+inline void interp1(const arma::vec& X, const arma::mat& Y, const arma::vec& XI, arma::mat& YI,
+                    double extrap_val = std::numeric_limits<double>::quiet_NaN(), Device& dev = Device::instance())
+{
+    if (Y.n_rows != X.n_elem) throw std::invalid_argument("interp1(): Y must have X.n_elem rows");
+    Interp1Axis(X, dev)(Y, XI, YI, extrap_val);
+}
+
 // Scattered bilinear interpolation (an extension, not an Armadillo call): ZI[k] = Z(YI[k], XI[k]); Z is
 // Y.n_elem x X.n_elem (rows follow Y), the layout arma::interp2 uses for its Z argument.  One result per query PAIR.
 // With the real Armadillo an arma::vec ZI binds here (exact match) rather than to the arma::mat overload below.
@@ -189,6 +235,25 @@ class GroupInterp1Table {
   private:
     DeviceGroup& grp_;
     mi_group_grid1* t_;
+};
+
+// interp1 over the columns of a matrix with the columns sharded over the group (Interp1Axis; X and XI replicated)
+class GroupInterp1Axis {
+  public:
+    GroupInterp1Axis(DeviceGroup& grp, const arma::vec& X) : grp_(grp), x_(X) {}
+    void operator()(const arma::mat& Y, const arma::vec& XI, arma::mat& YI,
+                    double extrap_val = std::numeric_limits<double>::quiet_NaN()) const
+    {
+        if (Y.n_rows != x_.n_elem) throw std::invalid_argument("interp1(): Y must have X.n_elem rows");
+        YI.set_size(XI.n_elem, Y.n_cols);
+        check(mi_group_interp1_cols_f64_host(grp_.get(), x_.memptr(), x_.n_elem, Y.memptr(), Y.n_rows, Y.n_cols, XI.memptr(),
+                                             XI.n_elem, YI.memptr(), XI.n_elem, extrap_val),
+              nullptr, "mi_group_interp1_cols_f64_host");
+    }
+
+  private:
+    DeviceGroup& grp_;
+    arma::vec x_;
 };
 
 // Bilinear interpolation over the group: Z = arma::mat(Y.n_elem, X.n_elem) replicated.  ZI an arma::vec: scattered

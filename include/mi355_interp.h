@@ -51,7 +51,9 @@ extern "C" {
  *              + mi_edm_set_kernel_choice (replaces two environment hooks), mi_edm_debug_counters,
  *                mi_group_set_gather_chunks;
  *              additive in 4: mi_interp2_grid_f64_dev, mi_interp2_grid_f64_host, mi_group_interp2_grid_f64_host (the
- *                gridded arma::interp2 output) */
+ *                gridded arma::interp2 output); mi_axis1_create, mi_axis1_create_uniform, mi_axis1_destroy,
+ *                mi_interp1_cols_f64_dev, mi_interp1_cols_f64_host, mi_group_interp1_cols_f64_host (interp1 over the
+ *                columns of a matrix: one X, many Y) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -67,6 +69,7 @@ enum {
 typedef struct mi_ctx mi_ctx;       /* one per device (+ stream)            */
 typedef struct mi_grid1 mi_grid1;   /* HBM-resident 1-D table               */
 typedef struct mi_grid2 mi_grid2;   /* HBM-resident 2-D table               */
+typedef struct mi_axis1 mi_axis1;   /* validated 1-D axis (nodes only)      */
 typedef struct mi_edm mi_edm;       /* EventDrivenMap device state          */
 typedef struct mi_timer mi_timer;   /* pair of HIP events on the ctx stream */
 
@@ -184,6 +187,36 @@ mi_status mi_interp2_grid_f64_dev(mi_ctx* ctx, const mi_grid2* g, const double* 
                                   const double* yi_dev, size_t nyi, double* zi_dev, double extrap_val);
 mi_status mi_interp2_grid_f64_host(mi_ctx* ctx, const mi_grid2* g, const double* xi, size_t nxi,
                                    const double* yi, size_t nyi, double* zi, double extrap_val);
+
+/* ---- interp1 over the columns of a matrix (one X, many Y) ---------------
+ * MATLAB's interp1 with a matrix Y; arma::interp1 takes vectors only, so this is the loop over the columns of an
+ * arma::mat that its callers write.  y is column-major n x ncols with leading dimension ldy >= n
+ * (arma::mat(n, ncols).memptr(), ldy = n), xi holds nxi queries in any order, yi is column-major nxi x ncols with
+ * leading dimension ldyi >= nxi:
+ *     yi[i + c*ldyi] == what mi_interp1_f64_dev returns for xi[i] on the table (x, y[:, c]),  bit for bit
+ * (extrap_val outside [x[0], x[n-1]], NaN for a NaN query, y[n-1, c] at x[n-1]; inf / NaN / -0.0 inside a column go
+ * through the two-term blend above and never reach another column).  Rows n..ldy-1 of y are never read, rows
+ * nxi..ldyi-1 of yi are never written.
+ *
+ * The axis is a handle of its own -- validated and uploaded once, reused while y changes from call to call.  x is NOT
+ * sorted or de-duplicated for the caller (that would mean permuting the rows of every y): this is Armadillo's
+ * "*linear" contract, and a non-increasing or non-finite x is MI_ERR_GRID, as mi_grid1_create without
+ * MI_GRID_SANITISE.  mi_axis1_create: flags = 0 or MI_GRID_DEVICE_PTRS (x is a device pointer, copied to the host
+ * once for validation).  mi_axis1_create_uniform: nodes fma(i, dx, x0), as mi_grid1_create_uniform.
+ *
+ * _dev: device pointers, 8-B aligned, asynchronous on the context's stream; allocates only to grow the context's
+ * record workspace (16 B per query, shared with mi_interp2_grid_f64_dev in stream order); ncols == 0 or nxi == 0 is
+ * MI_OK with nothing launched.  _host: host pointers, synchronous, columns go through in chunks.
+ * Which call when: many columns over one axis -> this call (each column is read once, each output written once).
+ * A single column with many queries (ncols == 1) is served faster by a mi_grid1 and mi_interp1_f64_dev, whose
+ * kernels read the queries and the table directly instead of going through 16-B records. */
+mi_status mi_axis1_create(mi_ctx* ctx, const double* x, size_t n, unsigned flags, mi_axis1** out);
+mi_status mi_axis1_create_uniform(mi_ctx* ctx, double x0, double dx, size_t n, mi_axis1** out);
+mi_status mi_axis1_destroy(mi_axis1* axis);
+mi_status mi_interp1_cols_f64_dev(mi_ctx* ctx, const mi_axis1* axis, const double* y_dev, size_t ldy, size_t ncols,
+                                  const double* xi_dev, size_t nxi, double* yi_dev, size_t ldyi, double extrap_val);
+mi_status mi_interp1_cols_f64_host(mi_ctx* ctx, const mi_axis1* axis, const double* y, size_t ldy, size_t ncols,
+                                   const double* xi, size_t nxi, double* yi, size_t ldyi, double extrap_val);
 
 /* ---- the reference's own interpolation ----------------------------------
  * Replaces RestrictKernel (EventDrivenMap.cu:769-785, launch :205-206):
@@ -398,6 +431,12 @@ mi_status mi_group_interp2_f64_dev(mi_group* g, const mi_group_grid2* t, const d
  * mi_shard_bounds(nxi, r, P), one contiguous slice of the column-major zi; yi is replicated.  Synchronous. */
 mi_status mi_group_interp2_grid_f64_host(mi_group* g, const mi_group_grid2* t, const double* xi, size_t nxi,
                                          const double* yi, size_t nyi, double* zi, double extrap_val);
+
+/* interp1 over the columns of a matrix, sharded by columns (mi_interp1_cols_f64_host): member r computes the columns
+ * [lo, hi) = mi_shard_bounds(ncols, r, P); x (n nodes, validated as by mi_axis1_create) and xi are replicated.  Host
+ * pointers, synchronous. */
+mi_status mi_group_interp1_cols_f64_host(mi_group* g, const double* x, size_t n, const double* y, size_t ldy, size_t ncols,
+                                         const double* xi, size_t nxi, double* yi, size_t ldyi, double extrap_val);
 
 /* EventDrivenMap with the realisations sharded over the group: p->n_real is the TOTAL (>= group size); shard r evolves
  * realisations [lo_r, hi_r) = mi_shard_bounds(n_real, r, P) with real_offset = p->real_offset + lo_r, so the per-neuron
