@@ -261,6 +261,10 @@ mi_status mi_interp1_pairs_f64_host(mi_ctx* ctx, const double* x, size_t ldx, co
  *   x_k = -L + 2L/ngrid * ind_k ;  out = x0 + (T-t0)*(x1-x0)/(t1-t0)   (fp32)
  * Arrays are [spike][realisation] (index m*R + r), n = S*R elements.  `out`
  * may alias t0 (the reference works in place).  Device pointers.
+ * The indices are read unsigned over the whole uint16 range, in any order
+ * (i1 < i0 and indices >= ngrid are plain arithmetic, not errors).  There is no
+ * guard for t1 == t0, exactly like the reference: the element is +-inf, or NaN
+ * where the numerator is 0 too; NaN / inf times propagate.
  */
 mi_status mi_restrict_f32_dev(mi_ctx* ctx, const float* t0, const uint16_t* i0, const float* t1,
                               const uint16_t* i1, float final_time, float half_length,
@@ -284,7 +288,13 @@ mi_status mi_restrict_f32_host(mi_ctx* ctx, const float* t0, const uint16_t* i0,
  * counted in the divisor (:822) -- unless count == 1, when it is summed whatever
  * its flag was.  In the partial block the sums never contain realisation 0 when
  * quirk is set and x0_m holds its restricted position (0 without quirk), so the
- * count == 1 rule can be applied to the total.  `accept` is never modified. */
+ * count == 1 rule can be applied to the total.  `accept` is never modified.
+ * count = sum of the flags; only a flag equal to 1 puts its realisation into the
+ * sums, so a flag > 1 is counted and not summed (that is what the clobbered
+ * accept[0] is).  count == 0 gives count 0 and every mean NaN (0/0, what the
+ * formula gives; with quirk too, realisation 0 re-enters for count == 1 only).
+ * A rejected realisation is selected away, not multiplied by 0: its values may
+ * be inf or NaN (Restrict with t1 == t0) without reaching a mean. */
 #define MI_EDM_PARTIAL_LEN(nspikes) (2 * (nspikes) + 1)
 mi_status mi_masked_mean_f32_dev(mi_ctx* ctx, const float* x, const uint32_t* accept, size_t nreal,
                                  size_t nspikes, int quirk, float* mean_dev, uint32_t* count_dev,
