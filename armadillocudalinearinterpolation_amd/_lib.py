@@ -48,6 +48,7 @@ _pp = C.POINTER(C.c_void_p)
 SIGNATURES = {
     "mi_abi_version": (_i32, []),
     "mi_debug_pinned_ranges": (_sz, []),
+    "mi_debug_sweep_ds_launches": (_sz, []),
     "mi_last_error": (C.c_char_p, [_vp]),
     "mi_ctx_create": (_i32, [_i32, _pp]),
     "mi_ctx_destroy": (_i32, [_vp]),
@@ -66,6 +67,7 @@ SIGNATURES = {
     "mi_grid1_destroy": (_i32, [_vp]),
     "mi_grid1_info": (_i32, [_vp, C.POINTER(_sz), C.POINTER(_i32), C.POINTER(_sz)]),
     "mi_interp1_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
+    "mi_interp1_f64_dev_v2": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
     "mi_interp1_f64_host": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
     "mi_interp1_f64": (_i32, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _dbl]),
     "mi_grid2_create": (_i32, [_vp, _vp, _sz, _vp, _sz, _vp, C.c_uint, _pp]),

@@ -185,7 +185,7 @@ class Grid1:
             out = torch.empty_like(xq)
         elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == xq.numel()):
             raise ValueError("out must be a contiguous float64 CUDA tensor of the same size")
-        check(self._L.mi_interp1_f64_dev(self._ctx._h, self._h, _ptr(xq), _ptr(out), xq.numel(), float(extrap)),
+        check(self._L.mi_interp1_f64_dev_v2(self._ctx._h, self._h, _ptr(xq), _ptr(out), xq.numel(), float(extrap)),
               self._ctx._h)
         return out
 

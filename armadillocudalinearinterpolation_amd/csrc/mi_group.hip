@@ -290,7 +290,7 @@ mi_status mi_group_interp1_f64_dev(mi_group* g, const mi_group_grid1* t, const d
     if (gathered_dev && g->gather_chunks > 1 && nq_per_shard >= 2 * (size_t)g->gather_chunks)
         return interp1_chunked_gather(g, t, xq_dev, yq_dev, nq_per_shard, extrap, gathered_dev);
     for (size_t r = 0; r < P; ++r) {
-        const mi_status st = mi_interp1_f64_dev(g->ctx[r], t->grid[r], xq_dev[r], yq_dev[r], nq_per_shard, extrap);
+        const mi_status st = mi_interp1_f64_dev_v2(g->ctx[r], t->grid[r], xq_dev[r], yq_dev[r], nq_per_shard, extrap);
         if (st != MI_OK) return st;
         if (gathered_dev && !g->distinct) MI_HIP(g->ctx[r], hipEventRecord(g->done[r], g->ctx[r]->stream));
     }
@@ -325,7 +325,7 @@ mi_status mi_group_interp1_f64_host(mi_group* g, const mi_group_grid1* t, const 
         if (st != MI_OK) break;
         herr = hipMemcpyAsync(c->scratch[0], xq + lo, bytes, hipMemcpyHostToDevice, c->stream);
         if (herr != hipSuccess) break;
-        st = mi_interp1_f64_dev(c, t->grid[r], (const double*)c->scratch[0], (double*)c->scratch[1], hi - lo, extrap);
+        st = mi_interp1_f64_dev_v2(c, t->grid[r], (const double*)c->scratch[0], (double*)c->scratch[1], hi - lo, extrap);
         if (st != MI_OK) break;
         herr = hipMemcpyAsync(yq + lo, c->scratch[1], bytes, hipMemcpyDeviceToHost, c->stream);
     }
@@ -442,7 +442,7 @@ static mi_status interp1_chunked_gather(mi_group* g, const mi_group_grid1* t, co
     for (size_t k = 0; k * c < nq_per_shard; ++k) {
         const size_t off = k * c, len = std::min(c, nq_per_shard - off);
         for (size_t r = 0; r < P; ++r) {
-            const mi_status st = mi_interp1_f64_dev(g->ctx[r], t->grid[r], xq_dev[r] + off, yq_dev[r] + off, len, extrap);
+            const mi_status st = mi_interp1_f64_dev_v2(g->ctx[r], t->grid[r], xq_dev[r] + off, yq_dev[r] + off, len, extrap);
             if (st != MI_OK) return st;
             MI_HIP(g->ctx[r], hipEventRecord(g->cdone[r][k], g->ctx[r]->stream));
         }

@@ -90,6 +90,8 @@ int mi_abi_version(void);
 /* Test hook: number of caller host ranges the library currently keeps page-locked on behalf of host-convenience calls
  * in flight (mi_interp1_f64_host, mi_interp2_f64_host); 0 once every such call has returned, on success or error. */
 size_t mi_debug_pinned_ranges(void);
+/* Test hook: launches of the deferred-store region sweep (mi_interp1_f64_dev_v2) by this process so far. */
+size_t mi_debug_sweep_ds_launches(void);
 /* Hint about the order of the query vectors handed to mi_interp1_f64_dev on this context.  Unordered queries
  * over a table larger than L2 are processed by a "region sweep" kernel (workgroup-local ordering by table region
  * in LDS; results keep the caller's order), ordered/clustered ones by the plain streaming kernel.  AUTO decides on
@@ -151,6 +153,12 @@ mi_status mi_grid1_info(const mi_grid1* g, size_t* n_nodes, int* mode, size_t* t
  */
 mi_status mi_interp1_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
                              size_t nq, double extrap_val);
+/* Same contract, same results bit for bit.  Where mi_interp1_f64_dev would run the pipelined region sweep as its only
+ * launch, this runs that kernel with part of each tile's result stores held back and issued beside the next tile's
+ * gathers (csrc/mi_sweep_ds.hip); every other call is forwarded to mi_interp1_f64_dev.  MI_SWEEP_DEFER=0 in the
+ * environment (read once per process) forwards every call. */
+mi_status mi_interp1_f64_dev_v2(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
+                                size_t nq, double extrap_val);
 /* Host convenience used by the arma::vec wrapper: uploads xq, runs, downloads
  * (synchronous). */
 mi_status mi_interp1_f64_host(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq,
