@@ -49,6 +49,7 @@ SIGNATURES = {
     "mi_abi_version": (_i32, []),
     "mi_debug_pinned_ranges": (_sz, []),
     "mi_debug_sweep_ds_launches": (_sz, []),
+    "mi_debug_grid1_formula": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "mi_last_error": (C.c_char_p, [_vp]),
     "mi_ctx_create": (_i32, [_i32, _pp]),
     "mi_ctx_destroy": (_i32, [_vp]),

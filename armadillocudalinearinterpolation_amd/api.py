@@ -174,7 +174,10 @@ class Grid1:
     def info(self):
         n, mode, tb = C.c_size_t(0), C.c_int(0), C.c_size_t(0)
         check(self._L.mi_grid1_info(self._h, C.byref(n), C.byref(mode), C.byref(tb)), self._ctx._h)
-        return {"n_nodes": n.value, "mode": mode.value, "table_bytes": tb.value}
+        formula, pin = C.c_int(0), C.c_int(0)
+        check(self._L.mi_debug_grid1_formula(self._h, C.byref(formula), C.byref(pin)), self._ctx._h)
+        return {"n_nodes": n.value, "mode": mode.value, "table_bytes": tb.value,
+                "formula": formula.value, "pin_last": pin.value}     # closed form of a mode-0 table (-1 otherwise)
 
     def interp(self, xq, out=None, extrap=math.nan):
         """xq: float64 cuda tensor -> float64 cuda tensor (asynchronous on the ctx stream)."""

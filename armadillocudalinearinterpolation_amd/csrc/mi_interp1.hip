@@ -100,7 +100,8 @@ mi_status launch_mode(mi_ctx* ctx, const G1Dev& d, size_t table_bytes, const dou
     if (MODE == 3) size_ok = table_bytes > kLdsMaxTableBytes && !(table_bytes > 2600000 && table_bytes < 3900000);
     if (sweep_env().min_bytes >= 0) size_ok = table_bytes >= (size_t)sweep_env().min_bytes;   // tuning hook
     // enough tiles for every CU to run a few sweeps (profiles/r02_strong_scaling_shards.log)
-    const bool sweep_ok = ctx->query_order != MI_QUERIES_ORDERED && size_ok &&
+    // (ntiles > 0: with MI_SWEEP_MIN_TILES_PER_CU=0 a call below one tile would otherwise launch a grid of no workgroups)
+    const bool sweep_ok = ctx->query_order != MI_QUERIES_ORDERED && size_ok && ntiles > 0 &&
                           ntiles >= (size_t)cus * sweep_env().min_tiles_per_cu && std::isfinite(d.xmax - d.xmin) && (d.xmax - d.xmin) > 0.0;
     if constexpr (MODE == 0 || MODE == 3) {
         // Whole table in LDS: unordered queries over a table that outgrows L1 (32 KiB) but fits LDS (128 KiB).

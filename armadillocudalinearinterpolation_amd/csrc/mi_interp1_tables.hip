@@ -334,4 +334,12 @@ mi_status mi_grid1_info(const mi_grid1* g, size_t* n_nodes, int* mode, size_t* t
     return MI_OK;
 }
 
+mi_status mi_debug_grid1_formula(const mi_grid1* g, int* formula, int* pin_last)
+{
+    MI_REQUIRE(nullptr, g != nullptr, "mi_debug_grid1_formula: grid is NULL");
+    if (formula) *formula = g->mode == 0 ? g->d.formula : -1;
+    if (pin_last) *pin_last = g->mode == 0 ? g->d.pin_last : -1;
+    return MI_OK;
+}
+
 }  // extern "C"

@@ -92,6 +92,10 @@ int mi_abi_version(void);
 size_t mi_debug_pinned_ranges(void);
 /* Test hook: launches of the deferred-store region sweep (mi_interp1_f64_dev_v2) by this process so far. */
 size_t mi_debug_sweep_ds_launches(void);
+/* Test hook: which closed form of the abscissae a mode-0 table evaluates (0 fma(i, dx, x0); 1 x0 + i*dx;
+ * 2 x0 + span*(i/(n-1)); 3 the same with the quotient from a Markstein step) and whether its last node is pinned to
+ * xmax -- i.e. which instance of the interp1 kernels a call on this table launches.  Both are -1 for the {x,y} modes. */
+mi_status mi_debug_grid1_formula(const mi_grid1* g, int* formula, int* pin_last);
 /* Hint about the order of the query vectors handed to mi_interp1_f64_dev on this context.  Unordered queries
  * over a table larger than L2 are processed by a "region sweep" kernel (workgroup-local ordering by table region
  * in LDS; results keep the caller's order), ordered/clustered ones by the plain streaming kernel.  AUTO decides on
