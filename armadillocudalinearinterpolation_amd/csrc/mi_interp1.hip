@@ -9,10 +9,13 @@
 //   interp1_order_probe       1024-sample test "are the queries already ordered?" (also inlined into the kernels).
 //   interp1_sweep_kernel      region sweep: persistent workgroups order a 16 K-query tile by table region in LDS so
 //   interp1_sweep_pipe_kernel that the whole chip gathers from the same part of the table at the same time.
-//                             Unordered queries over tables that outgrow L2 (and mid-size {x,y} tables).
+//                             Unordered queries over tables that outgrow L2 (and mid-size {x,y} tables).  The
+//                             pipelined form's DEFER parameter is what tells mi_interp1_f64_dev_v2 (part of each
+//                             tile's result stores held back) from mi_interp1_f64_dev (DEFER = 0).
 //                                                                                           (mi_interp1_sweep.hpp)
 // Tables: mi_interp1_tables.hip.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 
@@ -30,11 +33,12 @@ struct SweepEnv {
     size_t min_tiles_per_cu; // MI_SWEEP_MIN_TILES_PER_CU
     int variant;             // MI_SWEEP_VARIANT: 2 pipelined two-group form (default), 1 one phase after the other
     bool variant_forced;
+    int defer;               // MI_SWEEP_DEFER: 0 = mi_interp1_f64_dev_v2 runs what mi_interp1_f64_dev runs (A/B switch inside one library)
 };
 const SweepEnv& sweep_env()
 {
     static const SweepEnv e = [] {
-        SweepEnv v{-1, kSweepMinTilesPerCu, 2, false};
+        SweepEnv v{-1, kSweepMinTilesPerCu, 2, false, 1};
         if (const char* s = getenv("MI_SWEEP_MIN_BYTES")) v.min_bytes = (long)strtoull(s, nullptr, 10);
         if (const char* s = getenv("MI_SWEEP_MIN_TILES_PER_CU")) v.min_tiles_per_cu = (size_t)strtoull(s, nullptr, 10);
         if (const char* s = getenv("MI_SWEEP_VARIANT")) {
@@ -42,6 +46,7 @@ const SweepEnv& sweep_env()
             v.variant = (x == 1 || x == 2) ? x : 2;
             v.variant_forced = true;
         }
+        if (const char* s = getenv("MI_SWEEP_DEFER")) v.defer = atoi(s);
         return v;
     }();
     return e;
@@ -74,9 +79,13 @@ mi_status launch_vec(mi_ctx* ctx, const G1Dev& d, const double* xq, double* yq, 
     return launch_vec_shape<MODE, FORMULA, kBlock, kVecVpl>(ctx, d, xq, yq, nq, extrap, nullptr, probe);
 }
 
+std::atomic<size_t> g_ds_launches{0};      // mi_debug_sweep_ds_launches (test hook)
+
+// defer_stores: the caller is mi_interp1_f64_dev_v2 -- where the pipelined region sweep is the call's only launch, it
+// holds back part of each tile's result stores (DEFER = kSweepDefer(MODE)); every other choice is the same for both
 template <int MODE, int FORMULA = 0>
 mi_status launch_mode(mi_ctx* ctx, const G1Dev& d, size_t table_bytes, const double* xq, double* yq, size_t nq,
-                      double extrap)
+                      double extrap, bool defer_stores)
 {
     const bool aligned = ((reinterpret_cast<uintptr_t>(xq) | reinterpret_cast<uintptr_t>(yq)) & 15u) == 0;
     if (!aligned) {
@@ -159,7 +168,14 @@ mi_status launch_mode(mi_ctx* ctx, const G1Dev& d, size_t table_bytes, const dou
     // against 0.71 ms) and is 1 % behind at 3-12 tiles per CU (profiles/r02_strong_scaling_shards.log)
     if (sweep_env().variant == 2 && (sweep_env().variant_forced || ntiles >= (size_t)cus * 16)) {
         const unsigned pgrid = (unsigned)std::min<size_t>(ntiles, (size_t)cus);   // one 1024-lane workgroup per CU
-        hipLaunchKernelGGL((interp1_sweep_pipe_kernel<MODE, FORMULA>), dim3(pgrid), dim3(kPipeThreads), 0, ctx->stream, d, xq, yq,
+        if (defer_stores) {
+            hipLaunchKernelGGL((interp1_sweep_pipe_kernel<MODE, FORMULA, kSweepDefer(MODE)>), dim3(pgrid), dim3(kPipeThreads), 0,
+                               ctx->stream, d, xq, yq, ntiles, extrap, bscale, flags, nq - head, probe);
+            MI_LAUNCH_CHECK(ctx, "interp1 pipelined region-sweep kernel (deferred stores)");
+            g_ds_launches.fetch_add(1, std::memory_order_relaxed);
+            return MI_OK;
+        }
+        hipLaunchKernelGGL((interp1_sweep_pipe_kernel<MODE, FORMULA, 0>), dim3(pgrid), dim3(kPipeThreads), 0, ctx->stream, d, xq, yq,
                            ntiles, extrap, bscale, flags, nq - head, probe);
         MI_LAUNCH_CHECK(ctx, "interp1 pipelined region-sweep kernel");
         return MI_OK;
@@ -170,11 +186,8 @@ mi_status launch_mode(mi_ctx* ctx, const G1Dev& d, size_t table_bytes, const dou
     return MI_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-mi_status mi_interp1_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq, size_t nq, double extrap)
+// mi_interp1_f64_dev and mi_interp1_f64_dev_v2: the argument checks (one set of message texts) and the kernel choice
+mi_status interp1_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq, size_t nq, double extrap, bool defer_stores)
 {
     MI_REQUIRE(ctx, ctx && g, "mi_interp1_f64_dev: NULL context or grid");
     if (nq == 0) return MI_OK;
@@ -184,15 +197,31 @@ mi_status mi_interp1_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq, d
     MI_HIP(ctx, hipSetDevice(ctx->device));   // a process may hold contexts on several devices (mi_group)
     switch (g->mode) {
         case 0:
-            if (g->d.formula == 1) return launch_mode<0, 1>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap);
-            if (g->d.formula == 2) return launch_mode<0, 2>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap);
-            if (g->d.formula == 3) return launch_mode<0, 3>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap);
-            return launch_mode<0, 0>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap);
+            if (g->d.formula == 1) return launch_mode<0, 1>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap, defer_stores);
+            if (g->d.formula == 2) return launch_mode<0, 2>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap, defer_stores);
+            if (g->d.formula == 3) return launch_mode<0, 3>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap, defer_stores);
+            return launch_mode<0, 0>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap, defer_stores);
         case 1:
-            if (g->d.centred) return launch_mode<3>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap);
-            return launch_mode<1>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap);
-        default: return launch_mode<2>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap);
+            if (g->d.centred) return launch_mode<3>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap, defer_stores);
+            return launch_mode<1>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap, defer_stores);
+        default: return launch_mode<2>(ctx, g->d, g->table_bytes, xq, yq, nq, extrap, defer_stores);
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_debug_sweep_ds_launches(void) { return g_ds_launches.load(std::memory_order_relaxed); }
+
+mi_status mi_interp1_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq, size_t nq, double extrap)
+{
+    return interp1_dev(ctx, g, xq, yq, nq, extrap, false);
+}
+
+mi_status mi_interp1_f64_dev_v2(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq, size_t nq, double extrap)
+{
+    return interp1_dev(ctx, g, xq, yq, nq, extrap, sweep_env().defer != 0);
 }
 
 mi_status mi_interp1_f64_host(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq, size_t nq, double extrap)

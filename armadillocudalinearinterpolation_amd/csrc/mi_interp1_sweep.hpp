@@ -32,6 +32,24 @@ constexpr bool kSweepWin = false;    // mode 3: node G-1 on demand; fetching it 
 constexpr int kSweepThreads = 512;
 constexpr int kSweepK = 32;                               // queries per lane per tile
 constexpr int kSweepTile = kSweepThreads * kSweepK;       // queries per tile (8 B of LDS each)
+// exclusive prefix over the kSweepBins region counters, in place: one wave (lane = 0 .. 63), 64 counters at a time
+__device__ __forceinline__ void sweep_prefix_wave(unsigned* hist, int lane)
+{
+    unsigned run = 0;
+#pragma unroll
+    for (int base = 0; base < kSweepBins; base += 64) {
+        const unsigned v = hist[base + lane];
+        unsigned incl = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned o = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += o;
+        }
+        hist[base + lane] = run + incl - v;
+        run += __shfl(incl, 63, 64);
+    }
+}
+
 // (handing the gather chunks of a tile out dynamically to whichever wave is free was measured too: 0.711-0.716 ms against
 // 0.707-0.716 ms static -- the memory path returns in order, the wave that issued last finishes last whatever it was given)
 template <int MODE, int FORMULA>
@@ -70,21 +88,7 @@ __global__ __launch_bounds__(kSweepThreads) void interp1_sweep_kernel(G1Dev g, c
             rank[u] = (unsigned short)atomicAdd(&hist[b], 1u);
         }
         __syncthreads();
-        if (tid < 64) {                                   // exclusive prefix over the regions (one wave, 64 at a time)
-            unsigned run = 0;
-#pragma unroll
-            for (int base = 0; base < kSweepBins; base += 64) {
-                const unsigned v = hist[base + tid];
-                unsigned incl = v;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const unsigned o = __shfl_up(incl, off, 64);
-                    if (tid >= off) incl += o;
-                }
-                hist[base + tid] = run + incl - v;
-                run += __shfl(incl, 63, 64);
-            }
-        }
+        if (tid < 64) sweep_prefix_wave(hist, tid);
         __syncthreads();
         unsigned short sp[kSweepK];
 #pragma unroll
@@ -149,7 +153,8 @@ __global__ __launch_bounds__(kSweepThreads) void interp1_sweep_kernel(G1Dev g, c
 // loads issued by the gathering waves themselves (vmcnt is in order within a wave).  So: one 1024-lane workgroup per
 // CU, two groups of 8 waves that swap roles tile by tile.
 //   gatherer of tile t : gather + blend rounds over the sorted LDS tile (8 rounds of 4 queries per lane), reads its
-//                        results back, stores them (no wait) and issues the loads of tile t+2 into registers (no wait)
+//                        results back, stores them (no wait; DEFER of the 16 vectors per lane only at the start of its
+//                        next step) and issues the loads of tile t+2 into registers (no wait)
 //   preparer of tile t+1: its queries arrived in registers during the previous step; region histogram (LDS atomics,
 //                        its own histogram), prefix, sorted positions -- all while the other group gathers -- and the
 //                        scatter into the LDS tile once the gatherer has read its results out.
@@ -184,18 +189,60 @@ __device__ __forceinline__ void pipe_gather_rounds(const G1Dev& g, double* sq, i
     }
 }
 
+// result vectors held back per lane and tile (DEFER of interp1_sweep_pipe_kernel), by table mode: what fits the 128
+// registers without scratch ({x,y} tables have less room: their gather rounds keep more alive).  Timings of every DEFER
+// value and of both placements of the held-back stores, and which of them fit the 128 registers of a 1024-lane
+// workgroup without scratch: profiles/r08_sweep_deferred_stores.log.
+constexpr int kSweepDefer(int mode) { return mode == 0 ? 8 : 4; }
+
+typedef __attribute__((address_space(3))) volatile unsigned lds_vu32;
+
+// ragged tail (< one tile) of the pipelined form: one group of kPipeGroup lanes, four queries per lane at a time
+template <int MODE, int FORMULA>
+__device__ __forceinline__ void pipe_tail(const G1Dev& g, const double* tq, double* to, size_t tail, int tid, double extrap)
+{
+#pragma unroll 1
+    for (int u = 0; u < kSweepK; u += 4) {
+        double qq[4], rr[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const size_t i = (size_t)tid + (size_t)(u + w) * kPipeGroup;
+            qq[w] = i < tail ? tq[i] : 0.0;
+        }
+        eval_batch<MODE, 4, FORMULA, kSweepWin>(g, qq, rr, extrap);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const size_t i = (size_t)tid + (size_t)(u + w) * kPipeGroup;
+            if (i < tail) to[i] = rr[w];
+        }
+    }
+}
+
 // The gatherer issues all sixteen loads of its next tile right behind its result stores (one burst per tile).
 // Three workgroup barriers per tile: after the gather rounds, after the read-back, after the scatter.  The preparing
 // group orders its own histogram -> prefix -> positions passes with a counter in LDS that only its 8 waves touch, so
 // the gathering waves run their 8 rounds without stopping (barriers inside the rounds cost 1.2 us each: every
 // interval then ends with its slowest wave).
-template <int MODE, int FORMULA>
+//
+// DEFER: the hand-over of results.  With DEFER = 0 the group that has just gathered a tile stores its 16 result vectors
+// per lane and loads the 16 query vectors of its next tile in the gap while the other group scatters: 256 KiB per CU
+// through HBM with no gather in flight.  With DEFER > 0 it stores only 16 - DEFER vectors in the gap (their registers
+// become load destinations), issues all 16 loads (they stay in the gap: every measurement of moved loads lost), and
+// keeps DEFER result vectors in registers until the start of its next (prepare) step, where they go out beside the other
+// group's gather rounds (profiles/r02_exp_mix_stream_beside_gathers.log: streamed stores cost gathers 3 %).
+// Same tiles, same sort, same arithmetic (eval_batch), same store addresses, width and nt policy: the output is
+// bit-identical for every DEFER.  No wait of one workgroup on another; the only spin is the group counter.
+template <int MODE, int FORMULA, int DEFER>
 __global__ __launch_bounds__(kPipeThreads) void interp1_sweep_pipe_kernel(G1Dev g, const double* __restrict__ xq,
                                                                           double* __restrict__ yq, size_t ntiles,
                                                                           double extrap, double bscale,
                                                                           const int* __restrict__ order_flag,
                                                                           size_t tail, ProbeArgs probe)
 {
+    constexpr int kVec = kSweepK / 2;                      // result vectors per lane and tile
+    static_assert(DEFER >= 0 && DEFER <= kVec, "DEFER counts result vectors of a lane");
+    constexpr int kNow = kVec - DEFER;                     // stored in the gap
+    constexpr int kHeld = DEFER > 0 ? 2 * DEFER : 1;       // (an array of no elements is ill-formed)
     __shared__ double sq[kSweepTile];
     __shared__ unsigned hist[2][kSweepBins];
     __shared__ unsigned gbar[2];
@@ -206,25 +253,49 @@ __global__ __launch_bounds__(kPipeThreads) void interp1_sweep_pipe_kernel(G1Dev 
     const bool last_wg = blockIdx.x == gridDim.x - 1;
     if (probe.host_mailbox && last_wg && threadIdx.x >= kPipeThreads - 64) order_probe_wave(probe);   // for the next call
     const long nloc = ntiles > blockIdx.x ? (long)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x) : 0;
-    double q[kSweepK];                       // preparer: the tile's queries; gatherer: its results on their way out
+    double q[kSweepK];                       // preparer: the tile's queries; gatherer: the results that leave in the gap
+    double held[kHeld];                      // results held back from the gap to this group's next step
     unsigned sp2[kSweepK / 2];               // sorted positions of this group's tile, two per register
-    auto load_tile = [&](long it) {                          // the 16 vectors per lane of this group's next tile
-        const d2* q2 = reinterpret_cast<const d2*>(xq + ((size_t)blockIdx.x + (size_t)it * gridDim.x) * kSweepTile);
+    // `held` carries values from a gather step to the next prepare step only.  Zeros (constants, no register) on every
+    // other path, the way out of the loops included, so that the allocator has these registers for the sort.
+    auto drop_held = [&]() {
 #pragma unroll
-        for (int u = 0; u < kSweepK / 2; ++u) {
-            const d2 v = stream_load(q2 + tid + u * kPipeGroup);
+        for (int u = 0; u < kHeld; ++u) held[u] = 0.0;
+    };
+    drop_held();
+    // vector u of this lane in local tile `it` of a stream: a wave-uniform base and one 32-bit lane offset that the
+    // query and the result stream share (scalar-base addressing: no 64-bit lane address is kept across the loop)
+    const unsigned lane_bytes = (unsigned)tid * (unsigned)sizeof(d2);
+    auto vec_at = [&](const double* base, long it, int u) {
+        const char* row = reinterpret_cast<const char*>(base + ((size_t)blockIdx.x + (size_t)it * gridDim.x) * kSweepTile) +
+                          (size_t)u * kPipeGroup * sizeof(d2);
+        return reinterpret_cast<d2*>(const_cast<char*>(row + lane_bytes));
+    };
+    auto load_tile = [&](long it) {                          // the 16 vectors per lane of this group's next tile
+#pragma unroll
+        for (int u = 0; u < kVec; ++u) {
+            const d2 v = stream_load(vec_at(xq, it, u));
             q[2 * u] = v.x;
             q[2 * u + 1] = v.y;
         }
     };
-    auto store_tile = [&](long it) {
-        d2* o2 = reinterpret_cast<d2*>(yq + ((size_t)blockIdx.x + (size_t)it * gridDim.x) * kSweepTile);
+    auto store_now = [&](long it) {                          // vectors 0 .. kNow-1 of the tile, in the gap
 #pragma unroll
-        for (int u = 0; u < kSweepK / 2; ++u) {
+        for (int u = 0; u < kNow; ++u) {
             d2 v;
             v.x = q[2 * u];
             v.y = q[2 * u + 1];
-            stream_store(v, o2 + tid + u * kPipeGroup);
+            stream_store(v, vec_at(yq, it, u));
+        }
+    };
+    auto store_held = [&](long it) {                         // vectors kNow .. 15 of tile `it`, one step later
+        if (it < 0) return;                                  // (nothing gathered yet)
+#pragma unroll
+        for (int u = 0; u < DEFER; ++u) {
+            d2 v;
+            v.x = held[2 * u];
+            v.y = held[2 * u + 1];
+            stream_store(v, vec_at(yq, it, kNow + u));
         }
     };
     for (int b = threadIdx.x; b < 2 * kSweepBins; b += kPipeThreads) (&hist[0][0])[b] = 0;
@@ -237,7 +308,9 @@ __global__ __launch_bounds__(kPipeThreads) void interp1_sweep_pipe_kernel(G1Dev 
         gb_target += kPipeGroup / 64;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if ((threadIdx.x & 63) == 0) atomicAdd(&gbar[grp], 1u);
-        while (*reinterpret_cast<volatile unsigned*>(&gbar[grp]) < gb_target) __builtin_amdgcn_s_sleep(2);
+        // polled with an LDS load proper: a flat load counts as vector memory too, and waiting for its result would
+        // wait for every result store this wave has in flight
+        while (*(lds_vu32*)&gbar[grp] < gb_target) __builtin_amdgcn_s_sleep(2);
         asm volatile("" ::: "memory");
     };
     // One step of the schedule: in step `it` the owner of tile `it` (group it & 1) gathers it and the owner of tile
@@ -259,27 +332,36 @@ __global__ __launch_bounds__(kPipeThreads) void interp1_sweep_pipe_kernel(G1Dev 
             }
         }
         pipe_barrier();                      // (the preparer is done with its sort)
-        if (act) {                           // results out of the tile (own queries: positions remembered in sp2)
+        if (act) {                           // results out of the tile (own queries: positions remembered in sp2):
+                                             // into q (stored in the gap) or held (next step)
 #pragma unroll
             for (int u = 0; u < kSweepK; u += 2) {
-                q[u] = sq[sp2[u / 2] & 0xffffu];
-                q[u + 1] = sq[sp2[u / 2] >> 16];
+                const double a = sq[sp2[u / 2] & 0xffffu], b = sq[sp2[u / 2] >> 16];
+                if (u / 2 < kNow) {
+                    q[u] = a;
+                    q[u + 1] = b;
+                } else if constexpr (DEFER > 0) {
+                    held[u - 2 * kNow] = a;
+                    held[u + 1 - 2 * kNow] = b;
+                }
                 if ((u & 6) == 6) __builtin_amdgcn_sched_barrier(0);   // eight at a time: bounded register pressure
             }
         } else {
 #pragma unroll
             for (int u = 0; u < kSweepK; ++u) q[u] = 0.0;   // explicit definition on every path: q is dead during the rounds
+            drop_held();
         }
         pipe_barrier();
-        if (act) store_tile(it);             // results to HBM; nothing waited for
+        if (act) store_now(it);              // nothing waited for; the registers of these vectors take the loads below
         // Stores and loads are issued HERE, while nobody gathers (the other group scatters into LDS): measured against
         // leaving the last quarter / eighth of the loads (0.682 / 0.671 ms vs 0.672 ms) or all stores and loads (0.712 vs
         // 0.665 ms) to the start of this group's prepare step, where they would run beside the other group's gather rounds.
         // Also measured and dropped (profiles/r02_sweep_pipelined_phases.log): the preparer issuing its own loads in two
         // halves, one vector every 0.65 us, or one wave at a time -- they queue behind the gather requests of the other
         // group on the CU's one vector-memory path and land 9-19 us later (0.67-0.83 ms).
+        __builtin_amdgcn_sched_barrier(0);   // stores first: their registers are free when the loads want them
         if (it + 2 < nloc) {                 // (it = -1: group 1's first tile)
-            load_tile(it + 2);
+            load_tile(it + 2);               // all 16 loads stay in the gap, where nobody gathers
         } else {
 #pragma unroll
             for (int u = 0; u < kSweepK; ++u) q[u] = 0.0;
@@ -288,6 +370,11 @@ __global__ __launch_bounds__(kPipeThreads) void interp1_sweep_pipe_kernel(G1Dev 
     };
     auto prep_step = [&](long it) {          // this group owns tile it+1 (past the last tile: barriers only)
         const bool act = it + 1 < nloc;
+        // The results held back from tile it-1, which this group gathered in the previous step, go out here, beside the
+        // first gather rounds of the other group and behind this group's own loads, which are still landing.  (After
+        // the sort, in the slack before the barrier, the registers do not last: profiles/r08_sweep_deferred_stores.log.)
+        store_held(it - 1);
+        drop_held();
         unsigned rank2[kSweepK / 2];         // rank inside the region (histogram ticket), two per register
 #pragma unroll
         for (int u = 0; u < kSweepK / 2; ++u) rank2[u] = 0;
@@ -301,21 +388,7 @@ __global__ __launch_bounds__(kPipeThreads) void interp1_sweep_pipe_kernel(G1Dev 
                 if ((u & 6) == 6) __builtin_amdgcn_sched_barrier(0);
             }
             group_barrier();
-            if (tid < 64) {                  // exclusive prefix over the regions (one wave, 64 at a time)
-                unsigned run = 0;
-#pragma unroll
-                for (int base = 0; base < kSweepBins; base += 64) {
-                    const unsigned v = myhist[base + tid];
-                    unsigned incl = v;
-#pragma unroll
-                    for (int off = 1; off < 64; off <<= 1) {
-                        const unsigned o = __shfl_up(incl, off, 64);
-                        if (tid >= off) incl += o;
-                    }
-                    myhist[base + tid] = run + incl - v;
-                    run += __shfl(incl, 63, 64);
-                }
-            }
+            if (tid < 64) sweep_prefix_wave(myhist, tid);
             group_barrier();
 #pragma unroll
             for (int u = 0; u < kSweepK; u += 2) {   // sorted positions
@@ -362,25 +435,9 @@ __global__ __launch_bounds__(kPipeThreads) void interp1_sweep_pipe_kernel(G1Dev 
             if (++it >= nloc) break;
         }
     }
-    if (tail && last_wg && grp == 0) {       // ragged tail (< one tile), four queries per lane at a time
-        const double* tq = xq + ntiles * kSweepTile;
-        double* to = yq + ntiles * kSweepTile;
-#pragma unroll 1
-        for (int u = 0; u < kSweepK; u += 4) {
-            double qq[4], rr[4];
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const size_t i = (size_t)tid + (size_t)(u + w) * kPipeGroup;
-                qq[w] = i < tail ? tq[i] : 0.0;
-            }
-            eval_batch<MODE, 4, FORMULA, kSweepWin>(g, qq, rr, extrap);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const size_t i = (size_t)tid + (size_t)(u + w) * kPipeGroup;
-                if (i < tail) to[i] = rr[w];
-            }
-        }
-    }
+    // the group that gathered the workgroup's last tile has no prepare step left to store in
+    if (nloc > 0 && grp == (int)((nloc - 1) & 1)) store_held(nloc - 1);
+    if (tail && last_wg && grp == 0) pipe_tail<MODE, FORMULA>(g, xq + ntiles * kSweepTile, yq + ntiles * kSweepTile, tail, tid, extrap);
 }
 
 }  // namespace mi_interp1

@@ -154,13 +154,15 @@ mi_status mi_grid1_info(const mi_grid1* g, size_t* n_nodes, int* mode, size_t* t
  * L2 / Infinity Cache.
  * Generalises RestrictKernel's two-point blend (EventDrivenMap.cu:769-785) to
  * a tabulated grid with a gather index, as BASELINE.json's north_star asks.
+ * Kernel choice (launch_mode) and both entry points: csrc/mi_interp1.hip.
  */
 mi_status mi_interp1_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
                              size_t nq, double extrap_val);
-/* Same contract, same results bit for bit.  Where mi_interp1_f64_dev would run the pipelined region sweep as its only
- * launch, this runs that kernel with part of each tile's result stores held back and issued beside the next tile's
- * gathers (csrc/mi_sweep_ds.hip); every other call is forwarded to mi_interp1_f64_dev.  MI_SWEEP_DEFER=0 in the
- * environment (read once per process) forwards every call. */
+/* Same contract, same results bit for bit, same code (csrc/mi_interp1.hip: one dispatcher serves both).  Where
+ * mi_interp1_f64_dev runs the pipelined region sweep as its only launch, this runs that kernel with part of each tile's
+ * result stores held back and issued beside the next tile's gathers (interp1_sweep_pipe_kernel's DEFER parameter,
+ * csrc/mi_interp1_sweep.hpp); every other call does what mi_interp1_f64_dev does.  With MI_SWEEP_DEFER=0 in the
+ * environment (read once per process) every call does. */
 mi_status mi_interp1_f64_dev_v2(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
                                 size_t nq, double extrap_val);
 /* Host convenience used by the arma::vec wrapper: uploads xq, runs, downloads

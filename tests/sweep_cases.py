@@ -1,4 +1,4 @@
-"""Shared cases for the region-sweep kernels of interp1 (csrc/mi_interp1_sweep.hpp, csrc/mi_sweep_ds.hip): eight tables
+"""Shared cases for the region-sweep kernels of interp1 (csrc/mi_interp1_sweep.hpp): eight tables
 that between them reach every table mode and every closed form a test can reach, and one seeded query vector built
 tile by tile so that neighbouring tiles of a workgroup have sharply different region histograms.
 

@@ -17,11 +17,11 @@ INCLUDE = os.path.join(ROOT, "include")
 COLS = ["mi_interp1_cols_f64_dev", "mi_interp1_cols_f64_host", "mi_group_interp1_cols_f64_host"]
 AXIS = ["mi_axis1_create", "mi_axis1_create_uniform", "mi_axis1_destroy"]
 
-# _build.source_hash(family) of the commit this feature was built on; "interp1" since launch_mode refuses the sweep below
-# one tile and mi_debug_grid1_formula was added (host code only: no kernel of the family changed, and no entry of
-# profiles/traffic_latest.json is stamped with this family)
+# _build.source_hash(family) of the commit this feature was built on; "interp1" since the two copies of the pipelined region
+# sweep became one kernel with a DEFER parameter (mi_interp1_sweep.hpp) and mi_sweep_ds.hip's dispatch moved into launch_mode
+# (no entry of profiles/traffic_latest.json is stamped with this family: tests/test_sweep_ds_cpu.py)
 FAMILY_HASH = {
-    "interp1": "32cc259dcbd6e597629b8a72ca83cad5a62d20ed2c32e3d9f3a4333472b6bbeb",
+    "interp1": "296aad271a0904a9fdbdb9d0b52fb7b2dcb29ae98aa6951f44d490d3eb8cd97b",
     "interp2": "7158df4ee59207c26237d2add15161c66f70504f4f44d24a91fd9ccb39b19481",
     "edm": "c8f6d0461f0559c4061d947872b618de47ab96363ff449ed9b94f8c772715c66",
 }

@@ -1,5 +1,5 @@
 """GPU checks of mi_interp1_f64_dev_v2: the pipelined region sweep with part of each tile's result stores held back to the
-owning group's next step (csrc/mi_sweep_ds.hip) must reproduce the streaming kernel bit for bit, for every parity of the
+owning group's next step (DEFER > 0, csrc/mi_interp1_sweep.hpp) must reproduce the streaming kernel bit for bit, for every parity of the
 per-workgroup tile count, for workgroups with one tile or none, with and without a ragged tail, and must write nothing
 past the end of the result vector.
 

@@ -1,5 +1,5 @@
 """GPU checks of the three region-sweep kernels of interp1 -- the one-phase form and the pipelined two-group form
-(csrc/mi_interp1_sweep.hpp) and the deferred-store form (csrc/mi_sweep_ds.hip) -- on the cases of tests/sweep_cases.py:
+and its deferred-store form (DEFER > 0), both csrc/mi_interp1_sweep.hpp -- on the cases of tests/sweep_cases.py:
 eight tables (every table mode; closed forms 0, 1 and 3, with and without a pinned last node, asserted from the
 library's own answer) and a query vector whose tiles have sharply different region histograms (a whole tile in one
 region, only NaN, only out of range on one side, every node with its ulp neighbours, ...), so that the two tiles a
