@@ -544,6 +544,80 @@ def interp_pairs_host(ctx, X, Y, xi, lens=None, extrap=math.nan, want_ok=False):
                                            _ptr(ok) if want_ok else None), ctx._h)
     return (out, ok) if want_ok else out
 
+def interp_each(ctx, X, Y, XI, lens=None, out=None, extrap=math.nan, want_ok=False):
+    """interp1 over paired columns with a query vector per column (mi_interp1_each_f64_dev): column c of Y, sampled at
+    the nodes in column c of X, is evaluated at the queries in column c of XI.
+
+    X, Y, lens, out, the validation of X and the return value are interp_pairs'.  XI is either a column-major (nxi, B)
+    float64 CUDA view (Axis1's layout rules; its own leading dimension): the queries of each column -- or a contiguous
+    1-D float64 CUDA tensor of nxi queries shared by every column (ldxi = 0): bit-identical to interp_pairs, and served by
+    the thin one-lane-per-column kernel when the columns are very short.  Asynchronous on the context's stream."""
+    torch = _torch()
+    if not (XI.is_cuda and XI.dtype == torch.float64):
+        raise ValueError("XI must be a float64 CUDA tensor")
+    if not (X.is_cuda and X.dtype == torch.float64 and Y.is_cuda and Y.dtype == torch.float64):
+        raise ValueError("X and Y must be float64 CUDA tensors")
+    if X.dim() != 2 or tuple(X.shape) != tuple(Y.shape):
+        raise ValueError("X and Y must both have shape (n, B)")
+    n = int(X.shape[0])
+    ldx, B = Axis1._colmajor_view(X, n, "X")
+    ldy, _ = Axis1._colmajor_view(Y, n, "Y")
+    if XI.dim() == 1:
+        if not XI.is_contiguous():
+            raise ValueError("a shared XI must be a contiguous 1-D tensor")
+        nxi, ldxi = XI.numel(), 0
+    else:
+        if XI.dim() != 2:
+            raise ValueError("XI must be a column-major (nxi, B) view or a contiguous 1-D tensor")
+        nxi = int(XI.shape[0])
+        ldxi, Bq = Axis1._colmajor_view(XI, nxi, "XI")
+        if Bq != B:
+            raise ValueError("XI must have as many columns as X")
+    if lens is not None and not (lens.is_cuda and lens.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                 and lens.is_contiguous() and tuple(lens.shape) == (B,)):
+        raise ValueError("lens must be a contiguous int32 CUDA tensor of shape (B,)")
+    if out is None:
+        out = torch.empty((B, nxi), dtype=torch.float64, device=Y.device).T
+    elif not (out.is_cuda and out.dtype == torch.float64):
+        raise ValueError("out must be a float64 CUDA tensor")
+    ldyi, Bo = Axis1._colmajor_view(out, nxi, "out")
+    if Bo != B:
+        raise ValueError("out must have as many columns as Y")
+    ok = torch.empty((B,), dtype=torch.int32, device=Y.device) if want_ok else None
+    check(ctx._L.mi_interp1_each_f64_dev(ctx._h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, n,
+                                         C.c_void_p(lens.data_ptr()) if lens is not None else None, B,
+                                         C.c_void_p(XI.data_ptr()), ldxi, nxi, C.c_void_p(out.data_ptr()), ldyi, float(extrap),
+                                         C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
+    return (out, ok) if want_ok else out
+
+
+def _each_host_args(X, Y, XI, lens):
+    """the host forms' arguments: (X, Y, XI, lens, n, B, nxi, ldxi); a 2-D XI must be (nxi, B), a 1-D one is shared"""
+    XI = np.asarray(XI, dtype=np.float64)
+    if XI.ndim == 1:
+        X, Y, xi, lens, n, B = _pairs_host_args(X, Y, XI, lens)
+        return X, Y, xi, lens, n, B, xi.size, 0
+    X, Y, _, lens, n, B = _pairs_host_args(X, Y, np.zeros(0), lens)
+    if XI.ndim != 2 or XI.shape[1] != B:
+        raise ValueError("XI must have shape (nxi, B), one column of queries per column of X, or be 1-D")
+    XI = XI if XI.flags["F_CONTIGUOUS"] else np.asfortranarray(XI)
+    return X, Y, XI, lens, n, B, XI.shape[0], max(XI.shape[0], 1)
+
+
+def interp_each_host(ctx, X, Y, XI, lens=None, extrap=math.nan, want_ok=False):
+    """host form of interp_each (mi_interp1_each_f64_host): (n, B) numpy arrays, XI an (nxi, B) array (any layout;
+    column-major ones are used in place) or a 1-D array shared by every column; returns a Fortran-ordered (nxi, B) array,
+    or (array, ok) with want_ok=True.  Synchronous.  Without want_ok a bad column raises MiError (code 2, MI_ERR_GRID)."""
+    X, Y, XI, lens, n, B, nxi, ldxi = _each_host_args(X, Y, XI, lens)
+    out = np.empty((B, nxi)).T
+    ok = np.ones(B, dtype=np.uint32) if want_ok else None
+    check(ctx._L.mi_interp1_each_f64_host(ctx._h, C.c_void_p(X.ctypes.data), max(n, 1), C.c_void_p(Y.ctypes.data), max(n, 1), n,
+                                          _ptr(lens) if lens is not None else None, B, C.c_void_p(XI.ctypes.data), ldxi, nxi,
+                                          C.c_void_p(out.ctypes.data), max(nxi, 1), float(extrap),
+                                          _ptr(ok) if want_ok else None), ctx._h)
+    return (out, ok) if want_ok else out
+
+
 class EventDrivenMap:
     """Mirror of the reference class: ComputeF(Z) -> f through lift/evolve/restrict/average."""
 
@@ -818,6 +892,18 @@ class Group:
                                                       max(n, 1), n, _ptr(lens) if lens is not None else None, B, _ptr(xi),
                                                       xi.size, C.c_void_p(out.ctypes.data), max(xi.size, 1), float(extrap),
                                                       _ptr(ok) if want_ok else None))
+        return (out, ok) if want_ok else out
+
+    def interp_each_host(self, X, Y, XI, lens=None, extrap=math.nan, want_ok=False):
+        """interp1 over paired columns with a query vector per column (interp_each_host) with the columns sharded over
+        the group's devices; a 2-D XI is sharded with its columns, a 1-D one is replicated."""
+        X, Y, XI, lens, n, B, nxi, ldxi = _each_host_args(X, Y, XI, lens)
+        out = np.empty((B, nxi)).T
+        ok = np.ones(B, dtype=np.uint32) if want_ok else None
+        check(self._L.mi_group_interp1_each_f64_host(self._h, C.c_void_p(X.ctypes.data), max(n, 1), C.c_void_p(Y.ctypes.data),
+                                                     max(n, 1), n, _ptr(lens) if lens is not None else None, B,
+                                                     C.c_void_p(XI.ctypes.data), ldxi, nxi, C.c_void_p(out.ctypes.data),
+                                                     max(nxi, 1), float(extrap), _ptr(ok) if want_ok else None))
         return (out, ok) if want_ok else out
 
     def edm(self, parameters, noReal, **overrides):

@@ -752,6 +752,94 @@ mi_status mi_group_interp1_pairs_f64_host(mi_group* g, const double* x, size_t l
     return MI_OK;
 }
 
+// interp1 over paired columns with a query vector per column (mi_each1.hip), columns sharded as above; XI goes with its
+// columns when ldxi > 0 and is replicated when ldxi == 0.  Slots as in mi_interp1_each_f64_host: slot 0 the member's
+// columns of X then of Y, slot 1 XI (one vector, or the member's columns), len, col_ok, slot 2 its columns of YI.
+mi_status mi_group_interp1_each_f64_host(mi_group* g, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
+                                         const uint32_t* len, size_t ncols, const double* xi, size_t ldxi, size_t nxi,
+                                         double* yi, size_t ldyi, double extrap, uint32_t* col_ok)
+{
+    MI_REQUIRE(nullptr, g, "mi_group_interp1_each_f64_host: NULL group");
+    if (ncols == 0 || nxi == 0) return MI_OK;
+    MI_REQUIRE(nullptr, x && y && xi && yi, "mi_group_interp1_each_f64_host: NULL table/query/result pointer");
+    MI_REQUIRE(nullptr, n >= 2 && n < 0x7ffffff0u, "mi_group_interp1_each_f64_host: need 2 <= n < 2^31 - 16 (n=%zu)", n);
+    MI_REQUIRE(nullptr, ldx >= n, "mi_group_interp1_each_f64_host: ldx=%zu is smaller than n=%zu", ldx, n);
+    MI_REQUIRE(nullptr, ldy >= n, "mi_group_interp1_each_f64_host: ldy=%zu is smaller than n=%zu", ldy, n);
+    MI_REQUIRE(nullptr, ldyi >= nxi, "mi_group_interp1_each_f64_host: ldyi=%zu is smaller than nxi=%zu", ldyi, nxi);
+    MI_REQUIRE(nullptr, ldxi == 0 || ldxi >= nxi, "mi_group_interp1_each_f64_host: ldxi=%zu is smaller than nxi=%zu (0: one xi for every column)", ldxi, nxi);
+    const size_t lim = SIZE_MAX / (2 * sizeof(double)) / ncols;
+    MI_REQUIRE(nullptr, ldx <= lim && ldy <= lim && ldyi <= lim && ldxi <= lim && nxi <= lim,
+               "mi_group_interp1_each_f64_host: ncols=%zu x (ldx=%zu, ldy=%zu, ldxi=%zu, ldyi=%zu) too large", ncols, ldx, ldy, ldxi, ldyi);
+    const int P = (int)g->ctx.size();
+    const bool each = ldxi > 0;
+    std::vector<uint32_t> ok_own;
+    if (!col_ok) ok_own.resize(ncols);
+    uint32_t* const hok = col_ok ? col_ok : ok_own.data();
+    // page-locked above the size at which mi_interp1_each_f64_host starts to chunk, as mi_group_interp1_pairs_f64_host
+    const bool big = std::max(n, nxi) > 2 * ((size_t)8 << 20) / ncols;
+    const bool pin_q = big && mi::pin_host(xi, ((ncols - 1) * ldxi + nxi) * sizeof(double)),
+               pin_x = big && mi::pin_host(x, ((ncols - 1) * ldx + n) * sizeof(double)),
+               pin_y = big && mi::pin_host(y, ((ncols - 1) * ldy + n) * sizeof(double)),
+               pin_o = big && mi::pin_host(yi, ((ncols - 1) * ldyi + nxi) * sizeof(double));
+    mi_status st = MI_OK;
+    hipError_t herr = hipSuccess;
+    std::vector<size_t> q_bytes(P, 0);      // bytes of XI in front of len and col_ok in each member's slot 1
+    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
+        size_t lo, hi;
+        mi_shard_bounds(ncols, r, P, &lo, &hi);
+        if (hi == lo) continue;
+        mi_ctx* c = g->ctx[r];
+        herr = hipSetDevice(g->dev[r]);
+        if (herr != hipSuccess) break;
+        const size_t m = hi - lo;
+        const size_t xi_bytes = (each ? m * nxi : nxi) * sizeof(double);
+        q_bytes[r] = xi_bytes;
+        st = mi::ensure_scratch(c, 0, 2 * m * n * sizeof(double));
+        if (st == MI_OK) st = mi::ensure_scratch(c, 1, xi_bytes + 2 * m * sizeof(uint32_t));
+        if (st == MI_OK) st = mi::ensure_scratch(c, 2, m * nxi * sizeof(double));
+        if (st != MI_OK) break;
+        double *dx = (double*)c->scratch[0], *dy = dx + m * n, *dxi = (double*)c->scratch[1], *dyi = (double*)c->scratch[2];
+        uint32_t *dlen = (uint32_t*)((char*)c->scratch[1] + xi_bytes), *dok = dlen + m;
+        if (each) herr = group_copy_cols(dxi, nxi, xi + lo * ldxi, ldxi, nxi, m, hipMemcpyHostToDevice, c->stream);
+        else herr = hipMemcpyAsync(dxi, xi, xi_bytes, hipMemcpyHostToDevice, c->stream);
+        if (herr == hipSuccess && len) herr = hipMemcpyAsync(dlen, len + lo, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+        if (herr == hipSuccess) herr = group_copy_cols(dx, n, x + lo * ldx, ldx, n, m, hipMemcpyHostToDevice, c->stream);
+        if (herr == hipSuccess) herr = group_copy_cols(dy, n, y + lo * ldy, ldy, n, m, hipMemcpyHostToDevice, c->stream);
+        if (herr != hipSuccess) break;
+        st = mi_interp1_each_f64_dev(c, dx, n, dy, n, n, len ? dlen : nullptr, m, dxi, each ? nxi : 0, nxi, dyi, nxi, extrap, dok);
+        if (st != MI_OK) break;
+        herr = group_copy_cols(yi + lo * ldyi, ldyi, dyi, nxi, nxi, m, hipMemcpyDeviceToHost, c->stream);
+    }
+    // the flags last: their host side is not pinned, so this copy waits for the member's stream
+    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
+        size_t lo, hi;
+        mi_shard_bounds(ncols, r, P, &lo, &hi);
+        if (hi == lo) continue;
+        herr = hipSetDevice(g->dev[r]);
+        const uint32_t* dok = (const uint32_t*)((const char*)g->ctx[r]->scratch[1] + q_bytes[r]) + (hi - lo);
+        if (herr == hipSuccess) herr = hipMemcpyAsync(hok + lo, dok, (hi - lo) * sizeof(uint32_t), hipMemcpyDeviceToHost, g->ctx[r]->stream);
+    }
+    hipError_t esync = hipSuccess;
+    for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
+        (void)hipSetDevice(g->dev[r]);
+        const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
+        if (e != hipSuccess && esync == hipSuccess) esync = e;
+    }
+    if (pin_q) mi::unpin_host(xi);
+    if (pin_x) mi::unpin_host(x);
+    if (pin_y) mi::unpin_host(y);
+    if (pin_o) mi::unpin_host(yi);
+    if (st != MI_OK) return st;
+    if (herr != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_each_f64_host: copy failed: %s", hipGetErrorString(herr));
+    if (esync != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_each_f64_host: %s", hipGetErrorString(esync));
+    if (!col_ok)
+        for (size_t c = 0; c < ncols; ++c)
+            if (!hok[c])
+                return mi::fail(nullptr, MI_ERR_GRID, "mi_group_interp1_each_f64_host: column %zu is bad (len outside [2, n], or X not "
+                                "finite and strictly increasing; X is not sorted for the caller); its outputs are NaN", c);
+    return MI_OK;
+}
+
 // ---- EventDrivenMap -----------------------------------------------------------------------------------------------
 
 static mi_status edm_shard_params(const mi_group_edm* e, int r, mi_edm_params* p)

@@ -11,6 +11,10 @@
 //                                           per column: an ensemble of trajectories onto one mesh), YI = XI.n_elem x
 //                                           Y.n_cols; a column whose X is not finite and strictly increasing is all NaN
 //   mi355::GroupInterp1Paired gp(grp); gp(X, Y, XI, YI)   the same with the columns sharded over the GPUs of the node
+//   mi355::interp1_each(X, Y, XI, YI)       X, Y, XI, YI arma::mat: as interp1_paired with a query vector per column, column c
+//                                           of XI for column c of (X, Y); YI = XI.n_rows x Y.n_cols.  Very short columns
+//                                           (two-node Restrict-like tables) take a thin one-lane-per-column kernel
+//   mi355::GroupInterp1Each ge(grp); ge(X, Y, XI, YI)      the same with the columns (and XI's) sharded over the GPUs
 //   mi355::interp2(X, Y, Z, XI, YI, ZI)     ZI an arma::mat: == arma::interp2(X, Y, Z, XI, YI, ZI, "linear", extrap),
 //                                           ZI = YI.n_elem x XI.n_elem; Z = arma::mat(Y.n_elem, X.n_elem)
 //                                           ZI an arma::vec: scattered extension, one result per (XI[k], YI[k]) pair
@@ -168,6 +172,23 @@ inline void interp1_paired(const arma::mat& X, const arma::mat& Y, const arma::v
           dev.get(), "mi_interp1_pairs_f64_host");
 }
 
+// interp1 over paired columns with a query vector per column: YI(:, c) = arma::interp1(X.col(c), Y.col(c), XI.col(c),
+// YI.col(c), "*linear", extrap_val) for every column c.  Validation, NaN columns, ok and the throwing rule are
+// interp1_paired's; XI must have as many columns as X.
+inline void interp1_each(const arma::mat& X, const arma::mat& Y, const arma::mat& XI, arma::mat& YI,
+                         double extrap_val = std::numeric_limits<double>::quiet_NaN(), Device& dev = Device::instance(),
+                         std::vector<uint32_t>* ok = nullptr)
+{
+    if (X.n_rows != Y.n_rows || X.n_cols != Y.n_cols) throw std::invalid_argument("interp1_each(): X and Y must have the same shape");
+    if (XI.n_cols != X.n_cols) throw std::invalid_argument("interp1_each(): XI must have as many columns as X");
+    YI.set_size(XI.n_rows, Y.n_cols);
+    if (ok) ok->assign(Y.n_cols, 1u);
+    check(mi_interp1_each_f64_host(dev.get(), X.memptr(), X.n_rows, Y.memptr(), Y.n_rows, X.n_rows, nullptr, Y.n_cols,
+                                   XI.memptr(), XI.n_rows, XI.n_rows, YI.memptr(), XI.n_rows, extrap_val,
+                                   ok ? ok->data() : nullptr),
+          dev.get(), "mi_interp1_each_f64_host");
+}
+
 // Scattered bilinear interpolation (an extension, not an Armadillo call): ZI[k] = Z(YI[k], XI[k]); Z is
 // Y.n_elem x X.n_elem (rows follow Y), the layout arma::interp2 uses for its Z argument.  One result per query PAIR.
 // With the real Armadillo an arma::vec ZI binds here (exact match) rather than to the arma::mat overload below.
@@ -292,6 +313,27 @@ class GroupInterp1Paired {
                                               XI.memptr(), XI.n_elem, YI.memptr(), XI.n_elem, extrap_val,
                                               ok ? ok->data() : nullptr),
               nullptr, "mi_group_interp1_pairs_f64_host");
+    }
+
+  private:
+    DeviceGroup& grp_;
+};
+
+// interp1 over paired columns with a query vector per column, the columns of X, Y and XI sharded over the group
+class GroupInterp1Each {
+  public:
+    explicit GroupInterp1Each(DeviceGroup& grp) : grp_(grp) {}
+    void operator()(const arma::mat& X, const arma::mat& Y, const arma::mat& XI, arma::mat& YI,
+                    double extrap_val = std::numeric_limits<double>::quiet_NaN(), std::vector<uint32_t>* ok = nullptr) const
+    {
+        if (X.n_rows != Y.n_rows || X.n_cols != Y.n_cols) throw std::invalid_argument("interp1_each(): X and Y must have the same shape");
+        if (XI.n_cols != X.n_cols) throw std::invalid_argument("interp1_each(): XI must have as many columns as X");
+        YI.set_size(XI.n_rows, Y.n_cols);
+        if (ok) ok->assign(Y.n_cols, 1u);
+        check(mi_group_interp1_each_f64_host(grp_.get(), X.memptr(), X.n_rows, Y.memptr(), Y.n_rows, X.n_rows, nullptr, Y.n_cols,
+                                             XI.memptr(), XI.n_rows, XI.n_rows, YI.memptr(), XI.n_rows, extrap_val,
+                                             ok ? ok->data() : nullptr),
+              nullptr, "mi_group_interp1_each_f64_host");
     }
 
   private:

@@ -54,7 +54,10 @@ extern "C" {
  *                gridded arma::interp2 output); mi_axis1_create, mi_axis1_create_uniform, mi_axis1_destroy,
  *                mi_interp1_cols_f64_dev, mi_interp1_cols_f64_host, mi_group_interp1_cols_f64_host (interp1 over the
  *                columns of a matrix: one X, many Y); mi_interp1_pairs_f64_dev, mi_interp1_pairs_f64_host,
- *                mi_group_interp1_pairs_f64_host (interp1 over paired columns: every column of Y with its own X) */
+ *                mi_group_interp1_pairs_f64_host (interp1 over paired columns: every column of Y with its own X);
+ *                mi_interp1_each_f64_dev, mi_interp1_each_f64_host, mi_group_interp1_each_f64_host,
+ *                mi_debug_each_launches (paired columns with a query vector per column, and a thin kernel for very
+ *                short columns) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -92,6 +95,9 @@ int mi_abi_version(void);
 size_t mi_debug_pinned_ranges(void);
 /* Test hook: launches of the deferred-store region sweep (mi_interp1_f64_dev_v2) by this process so far. */
 size_t mi_debug_sweep_ds_launches(void);
+/* Test hook: calls of mi_interp1_each_f64_dev by this process so far that took the given form: 0 thin kernel, 1 LDS
+ * form, 2 direct form, 3 forwarded to mi_interp1_pairs_f64_dev; 0 for any other value of form. */
+size_t mi_debug_each_launches(int form);
 /* Test hook: which closed form of the abscissae a mode-0 table evaluates (0 fma(i, dx, x0); 1 x0 + i*dx;
  * 2 x0 + span*(i/(n-1)); 3 the same with the quotient from a Markstein step) and whether its last node is pinned to
  * xmax -- i.e. which instance of the interp1 kernels a call on this table launches.  Both are -1 for the {x,y} modes. */
@@ -269,6 +275,34 @@ mi_status mi_interp1_pairs_f64_dev(mi_ctx* ctx, const double* x_dev, size_t ldx,
 mi_status mi_interp1_pairs_f64_host(mi_ctx* ctx, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
                                     const uint32_t* len, size_t ncols, const double* xi, size_t nxi, double* yi,
                                     size_t ldyi, double extrap_val, uint32_t* col_ok);
+
+/* ---- interp1 over paired columns, a query vector per column ---------------
+ * mi_interp1_pairs_f64_dev with an XI per column: an ensemble of independent tables, each with its own X, Y and XI.
+ * Inverse-CDF sampling from ncols distributions (column c of x a CDF, of y its quantiles, of xi that distribution's
+ * uniform draws); every trajectory resampled onto a time mesh of its own; Restrict with a horizon per realisation.
+ * The contract is mi_interp1_pairs_f64_dev's word for word -- x, y, yi, len, n_c, the BAD-column rule (all nxi outputs
+ * NaN, no other column affected), col_ok, alignment, the empty calls, the status rule of the _host form -- with one
+ * change: xi is column-major nxi x ncols with leading dimension ldxi >= nxi, 8-B aligned, and
+ *     yi[i + c*ldyi] == what mi_interp1_f64_dev returns for xi[i + c*ldxi] on the table (x[0:n_c, c], y[0:n_c, c]) built
+ *                       without MI_GRID_SANITISE,  bit for bit.
+ * Rows nxi..ldxi-1 of xi are never read; yi must not overlap an input.
+ * ldxi == 0 means ONE xi vector (nxi doubles) for every column: the results are bit-identical to
+ * mi_interp1_pairs_f64_dev's.  0 < ldxi < nxi is MI_ERR_INVALID_ARG, and ldxi takes part in the byte-count overflow check.
+ * Very short columns (n and nxi both small; the reference's RestrictKernel shape n = 2, nxi = 1 among them) are served
+ * by a thin kernel, one lane per column, whatever ldxi is -- for one shared xi this call with ldxi == 0 is the way to it;
+ * longer columns with ldxi == 0 are handed to mi_interp1_pairs_f64_dev unchanged.
+ * _dev: asynchronous on the context's stream, no copy, no synchronisation.  Allocation: none for n <= 4096; for longer
+ * columns with ldxi > 0 the validation flags go into col_ok_dev when given, otherwise into the context's record
+ * workspace, exactly as in mi_interp1_pairs_f64_dev.
+ * _host: host pointers, synchronous, pinned and pipelined column chunks; with ldxi > 0 xi travels with its columns.
+ * Which call when: an X AND an XI per column, or very short columns (n <= 32 and nxi <= 8: kThinMaxN, kThinMaxQ in csrc/mi_each1.hip) -> this call; an X per column
+ * and one XI -> mi_interp1_pairs_f64_dev; one X for every column -> mi_interp1_cols_f64_dev. */
+mi_status mi_interp1_each_f64_dev(mi_ctx* ctx, const double* x_dev, size_t ldx, const double* y_dev, size_t ldy, size_t n,
+                                  const uint32_t* len_dev, size_t ncols, const double* xi_dev, size_t ldxi, size_t nxi,
+                                  double* yi_dev, size_t ldyi, double extrap_val, uint32_t* col_ok_dev);
+mi_status mi_interp1_each_f64_host(mi_ctx* ctx, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
+                                   const uint32_t* len, size_t ncols, const double* xi, size_t ldxi, size_t nxi, double* yi,
+                                   size_t ldyi, double extrap_val, uint32_t* col_ok);
 
 /* ---- the reference's own interpolation ----------------------------------
  * Replaces RestrictKernel (EventDrivenMap.cu:769-785, launch :205-206):
@@ -506,6 +540,13 @@ mi_status mi_group_interp1_cols_f64_host(mi_group* g, const double* x, size_t n,
 mi_status mi_group_interp1_pairs_f64_host(mi_group* g, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
                                           const uint32_t* len, size_t ncols, const double* xi, size_t nxi, double* yi,
                                           size_t ldyi, double extrap_val, uint32_t* col_ok);
+
+/* interp1 over paired columns with a query vector per column, sharded by columns (mi_interp1_each_f64_host): member r
+ * computes the columns [lo, hi) = mi_shard_bounds(ncols, r, P); xi is sharded with the columns when ldxi > 0 and
+ * replicated when ldxi == 0.  Otherwise as mi_group_interp1_pairs_f64_host. */
+mi_status mi_group_interp1_each_f64_host(mi_group* g, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
+                                         const uint32_t* len, size_t ncols, const double* xi, size_t ldxi, size_t nxi,
+                                         double* yi, size_t ldyi, double extrap_val, uint32_t* col_ok);
 
 /* EventDrivenMap with the realisations sharded over the group: p->n_real is the TOTAL (>= group size); shard r evolves
  * realisations [lo_r, hi_r) = mi_shard_bounds(n_real, r, P) with real_offset = p->real_offset + lo_r, so the per-neuron
