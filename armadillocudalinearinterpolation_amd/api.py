@@ -618,6 +618,50 @@ def interp_each_host(ctx, X, Y, XI, lens=None, extrap=math.nan, want_ok=False):
     return (out, ok) if want_ok else out
 
 
+def _cube_view(a, rows, cols, what):
+    """(leading dimension, slice stride, slices) of a 3-D (rows, cols, S) array or tensor stored like an arma::cube:
+    element (i, j, s) at i + j*ld + s*stride, i.e. the .permute(2, 1, 0) view of a contiguous (S, cols, rows) buffer, or
+    a padded view of one; strides in elements"""
+    shape = tuple(a.shape)
+    if len(shape) != 3 or shape[0] != rows or shape[1] != cols:
+        raise ValueError("%s must have shape (%d, %d, S)" % (what, rows, cols))
+    st = a.stride() if hasattr(a, "stride") else tuple(s // a.itemsize for s in a.strides)
+    S = shape[2]
+    ld = st[1] if cols > 1 else max(rows, 1)
+    stride = st[2] if S > 1 else ld * cols
+    if (rows > 1 and st[0] != 1) or ld < rows or stride < ld * cols:
+        raise ValueError("%s must be stored slice by slice, column-major inside a slice (the .permute(2, 1, 0) view of a "
+                         "contiguous (S, %d, %d) buffer)" % (what, cols, rows))
+    return ld, stride, S
+
+
+def interp2_slices(ctx, ax, ay, Z, xi, yi, out=None, extrap=math.nan):
+    """mi_interp2_slices_f64_dev: arma::interp2's gridded output for every slice of a cube, Z read where it lies.
+    ax, ay: Axis1 (nx and ny nodes; the same object is allowed); Z: (ny, nx, S) float64 CUDA tensor laid out like an
+    arma::cube (see _cube_view; a padded view is taken as it is); xi, yi: contiguous float64 CUDA tensors in any order;
+    out: (nyi, nxi, S) tensor of the same layout (default: the .permute(2, 1, 0) view of a new contiguous (S, nxi, nyi)
+    buffer).  Returns out with out[i, j, s] = Z[:, :, s] at (xi[j], yi[i]), bit-identical to Grid2.interp_grid on that
+    slice; asynchronous on the context's stream."""
+    torch = _torch()
+    for t in (xi, yi):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+            raise ValueError("query axes must be contiguous float64 CUDA tensors")
+    if not (Z.is_cuda and Z.dtype == torch.float64):
+        raise ValueError("Z must be a float64 CUDA tensor")
+    ldz, zstride, S = _cube_view(Z, ay.n, ax.n, "Z")
+    nxi, nyi = xi.numel(), yi.numel()
+    if out is None:
+        out = torch.empty((S, nxi, nyi), dtype=torch.float64, device=Z.device).permute(2, 1, 0)
+    elif not (out.is_cuda and out.dtype == torch.float64):
+        raise ValueError("out must be a float64 CUDA tensor")
+    ldzi, zistride, So = _cube_view(out, nyi, nxi, "out")
+    if So != S:
+        raise ValueError("out must have as many slices as Z")
+    check(ctx._L.mi_interp2_slices_f64_dev(ctx._h, ax._h, ay._h, C.c_void_p(Z.data_ptr()), ldz, zstride, S, _ptr(xi), nxi,
+                                           _ptr(yi), nyi, C.c_void_p(out.data_ptr()), ldzi, zistride, float(extrap)), ctx._h)
+    return out
+
+
 class EventDrivenMap:
     """Mirror of the reference class: ComputeF(Z) -> f through lift/evolve/restrict/average."""
 

@@ -34,14 +34,7 @@
 #include <vector>
 
 #include "mi_interp2_eval.hpp"
-
-struct mi_axis1 {
-    mi_ctx* ctx;
-    int device;            // copied at creation: destroy must not dereference a context that may be gone
-    void* dev_x;           // explicit nodes (null for a uniform axis)
-    AxisDev a;
-    size_t n;
-};
+#include "mi_axis1.hpp"
 
 namespace mi_cols1 {
 

@@ -57,7 +57,8 @@ extern "C" {
  *                mi_group_interp1_pairs_f64_host (interp1 over paired columns: every column of Y with its own X);
  *                mi_interp1_each_f64_dev, mi_interp1_each_f64_host, mi_group_interp1_each_f64_host,
  *                mi_debug_each_launches (paired columns with a query vector per column, and a thin kernel for very
- *                short columns) */
+ *                short columns); mi_interp2_slices_f64_dev, mi_debug_slices2_launches (gridded interp2 over the slices of a
+ *                cube, Z read in place; device form) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -98,6 +99,10 @@ size_t mi_debug_sweep_ds_launches(void);
 /* Test hook: calls of mi_interp1_each_f64_dev by this process so far that took the given form: 0 thin kernel, 1 LDS
  * form, 2 direct form, 3 forwarded to mi_interp1_pairs_f64_dev; 0 for any other value of form. */
 size_t mi_debug_each_launches(int form);
+/* Test hook: calls of mi_interp2_slices_f64_dev by this process so far that took the given form: 0 LDS form with the
+ * tile body, 1 LDS form with the flat body (thin outputs, nyi < 256), 2 direct form with the tile body, 3 direct form
+ * with the flat body; 0 for any other value of form. */
+size_t mi_debug_slices2_launches(int form);
 /* Test hook: which closed form of the abscissae a mode-0 table evaluates (0 fma(i, dx, x0); 1 x0 + i*dx;
  * 2 x0 + span*(i/(n-1)); 3 the same with the quotient from a Markstein step) and whether its last node is pinned to
  * xmax -- i.e. which instance of the interp1 kernels a call on this table launches.  Both are -1 for the {x,y} modes. */
@@ -303,6 +308,38 @@ mi_status mi_interp1_each_f64_dev(mi_ctx* ctx, const double* x_dev, size_t ldx, 
 mi_status mi_interp1_each_f64_host(mi_ctx* ctx, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
                                    const uint32_t* len, size_t ncols, const double* xi, size_t ldxi, size_t nxi, double* yi,
                                    size_t ldyi, double extrap_val, uint32_t* col_ok);
+
+/* ---- gridded interp2 over the slices of a cube, Z read in place -------------
+ * arma::interp2 in a loop over the slices of an arma::cube: an ensemble of 2-D fields regridded onto another mesh, a
+ * field that lives on the device and changes from step to step.  Two axes (mi_axis1: nx = ax->n and ny = ay->n nodes;
+ * ax == ay is allowed) and a stack of nslices plain column-major matrices, the layout of
+ * arma::cube(ny, nx, nslices).memptr():
+ *     Z_s(i, j) = z[i + j*ldz + s*z_slice_stride],     ny x nx,   ldz >= ny,   z_slice_stride >= ldz*nx,
+ *     ZI_s(i, j) = zi[i + j*ldzi + s*zi_slice_stride], nyi x nxi, ldzi >= nyi, zi_slice_stride >= ldzi*nxi
+ * (both strides are ignored for nslices <= 1), and
+ *     zi[i + j*ldzi + s*zi_slice_stride] == what mi_interp2_grid_f64_dev returns at (xi[j], yi[i]) on a mi_grid2 built
+ *                                           from (x, y, Z_s),  bit for bit:
+ * oracle/interp_oracle.c orc_interp2_bilinear -- the four corners Z(ly,lx), Z(ry,lx), Z(ly,rx), Z(ry,rx) with
+ * r = min(l+1, n-1), the blend along y inside both columns, then along x, every product and sum rounded (no FMA),
+ * extrap_val outside either axis, NaN for a NaN coordinate.  xi and yi may be in any order.  Rows ny..ldz-1 of z and the
+ * gap between slices are never read; rows nyi..ldzi-1 of zi and the gap between slices are never written; zi must not
+ * overlap an input.  inf, NaN and -0.0 inside a slice go through the blend; they never reach another slice, or an output
+ * whose four corners do not include them.
+ * _dev: device pointers, 8-B aligned; asynchronous on the context's stream, no copy, no synchronisation; the only
+ * allocation grows the context's record workspace ((nxi + nyi) x 16 B, shared in stream order with
+ * mi_interp2_grid_f64_dev, mi_interp1_cols_f64_dev and the long-column forms of the paired-column calls); nslices == 0,
+ * nxi == 0 or nyi == 0 is MI_OK with nothing launched or written.  Each coordinate is located once per call for all
+ * slices; one kernel follows, which reads each slice once into LDS when it holds at most 8192 elements and gathers the
+ * corners from the slice itself otherwise (csrc/mi_slices2.hip; mi_debug_slices2_launches tells which).
+ * MI_ERR_INVALID_ARG for NULL or misaligned pointers, an axis of another device than the context's, ldz < ny,
+ * ldzi < nyi, a slice stride smaller than its matrix (nslices > 1), sizes whose byte counts overflow.
+ * There is no host-pointer or group form of this call yet.
+ * Which call when: one table that answers many calls -> mi_grid2 and mi_interp2_grid_f64_dev (its resident layout gives
+ * one 32-B cell per output); a Z that changes on the device, or many slices over one pair of axes -> this call. */
+mi_status mi_interp2_slices_f64_dev(mi_ctx* ctx, const mi_axis1* ax, const mi_axis1* ay, const double* z_dev, size_t ldz,
+                                    size_t z_slice_stride, size_t nslices, const double* xi_dev, size_t nxi,
+                                    const double* yi_dev, size_t nyi, double* zi_dev, size_t ldzi, size_t zi_slice_stride,
+                                    double extrap_val);
 
 /* ---- the reference's own interpolation ----------------------------------
  * Replaces RestrictKernel (EventDrivenMap.cu:769-785, launch :205-206):
