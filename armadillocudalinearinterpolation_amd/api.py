@@ -333,7 +333,12 @@ class Axis1:
     Layout, as arma::mat: Y is (n, B) with one profile per COLUMN, stored column-major -- element (i, c) at
     i + c*ld -- and so is the (nxi, B) result.  In torch / numpy terms that is the .T view of a C-contiguous (B, n)
     buffer (a realisation per row of the buffer); a view with a row stride ld > n (buffer[:, :n].T) is taken as it is.
-    X is used as given ("*linear" contract): strictly increasing and finite, else MiError (MI_ERR_GRID)."""
+    X is used as given ("*linear" contract): strictly increasing and finite, else MiError (MI_ERR_GRID).
+
+    Data stored the other way round -- one table per ROW of a column-major (m, n) matrix, i.e. a C-contiguous (n, m)
+    "time-major" buffer viewed .T, every time level a contiguous block -- goes through interp_rows, and a cube of fields
+    at n time levels through interp_stack (interpolation along the slice index); both are one call of
+    mi_interp1_rows_f64_dev and bit-identical to interp_cols on the transposed data.  Device tensors only."""
 
     def __init__(self, ctx, handle, n):
         self._ctx, self._h, self._L, self.n = ctx, handle, ctx._L, int(n)
@@ -394,6 +399,85 @@ class Axis1:
             raise ValueError("out must have as many columns as Y")
         check(self._L.mi_interp1_cols_f64_dev(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, B, _ptr(xi), nxi,
                                               C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
+        return out
+
+    @staticmethod
+    def _rows_view(a, cols, what):
+        """(leading dimension, rows) of a 2-D (m, cols) array or tensor stored column-major, one table per row: element
+        (r, k) at r + k*ld, the .T view of a C-contiguous (cols, m) buffer or a padded view of one (buffer[:, :m].T);
+        strides in elements"""
+        shape = tuple(a.shape)
+        if len(shape) != 2 or shape[1] != cols:
+            raise ValueError("%s must have shape (m, %d)" % (what, cols))
+        st = a.stride() if hasattr(a, "stride") else tuple(s // a.itemsize for s in a.strides)
+        m = shape[0]
+        ld = st[1] if cols > 1 else max(m, 1)
+        if (m > 1 and st[0] != 1) or ld < m:
+            raise ValueError("%s must be column-major (the .T view of a contiguous (%d, m) buffer)" % (what, cols))
+        return ld, m
+
+    @staticmethod
+    def _stack_view(a, what):
+        """(ny, nx, slice stride, slices) of a 3-D (ny, nx, S) array or tensor laid out like an arma::cube (_cube_view)
+        whose slices are dense, ldz == ny: the ny*nx elements of a slice are then one column of a (ny*nx, S) matrix
+        with the slice stride as its leading dimension"""
+        shape = tuple(a.shape)
+        if len(shape) != 3:
+            raise ValueError("%s must have shape (ny, nx, S)" % what)
+        ny, nx = shape[0], shape[1]
+        ld, stride, S = _cube_view(a, ny, nx, what)
+        if ld != ny:
+            raise ValueError("%s: the slices must be dense (ldz == ny); this view has ldz = %d > ny = %d" % (what, ld, ny))
+        return ny, nx, stride, S
+
+    def interp_rows(self, Y, xi, out=None, extrap=math.nan):
+        """mi_interp1_rows_f64_dev: one table per ROW.  Y: (m, n) float64 CUDA tensor stored column-major (the .T view of
+        a C-contiguous (n, m) buffer, or a padded view of one); xi: contiguous float64 CUDA tensor of nxi queries in any
+        order; out: (m, nxi) tensor in the same layout (default: the .T view of a new contiguous (nxi, m) buffer).
+        Returns out with out[r, i] = interp1 of xi[i] on (X, Y[r, :]), bit-identical to interp_cols on the transposed
+        data; asynchronous on the context's stream."""
+        torch = _torch()
+        ldy, m = self._rows_view(Y, self.n, "Y")
+        if not (xi.is_cuda and xi.dtype == torch.float64 and xi.is_contiguous()):
+            raise ValueError("xi must be a contiguous float64 CUDA tensor")
+        if not (Y.is_cuda and Y.dtype == torch.float64):
+            raise ValueError("Y must be a float64 CUDA tensor")
+        nxi = xi.numel()
+        if out is None:
+            out = torch.empty((nxi, m), dtype=torch.float64, device=Y.device).T
+        elif not (out.is_cuda and out.dtype == torch.float64):
+            raise ValueError("out must be a float64 CUDA tensor")
+        ldyi, mo = self._rows_view(out, nxi, "out")
+        if mo != m:
+            raise ValueError("out must have as many rows as Y")
+        check(self._L.mi_interp1_rows_f64_dev(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, m, _ptr(xi), nxi,
+                                              C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
+        return out
+
+    def interp_stack(self, Z, ti, out=None, extrap=math.nan):
+        """interp1 across the slices of a cube: Z is a (ny, nx, S) float64 CUDA tensor laid out like an arma::cube
+        (_cube_view) with S == n fields, one per node of this axis, and dense slices (ldz == ny, else ValueError; the slice
+        stride may exceed ny*nx); ti: contiguous float64 CUDA tensor of nti times in any order; out: (ny, nx, nti) tensor
+        of the same layout (default: the .permute(2, 1, 0) view of a new contiguous (nti, nx, ny) buffer).  Returns out
+        with out[i, j, k] = interp1 of ti[k] on (X, Z[i, j, :]): one call of mi_interp1_rows_f64_dev with m = ny*nx."""
+        torch = _torch()
+        ny, nx, zstride, S = self._stack_view(Z, "Z")
+        if S != self.n:
+            raise ValueError("Z must hold one slice per node of the axis (%d), not %d" % (self.n, S))
+        if not (ti.is_cuda and ti.dtype == torch.float64 and ti.is_contiguous()):
+            raise ValueError("ti must be a contiguous float64 CUDA tensor")
+        if not (Z.is_cuda and Z.dtype == torch.float64):
+            raise ValueError("Z must be a float64 CUDA tensor")
+        nti = ti.numel()
+        if out is None:
+            out = torch.empty((nti, nx, ny), dtype=torch.float64, device=Z.device).permute(2, 1, 0)
+        elif not (out.is_cuda and out.dtype == torch.float64):
+            raise ValueError("out must be a float64 CUDA tensor")
+        oy, ox, ostride, So = self._stack_view(out, "out")
+        if (oy, ox, So) != (ny, nx, nti):
+            raise ValueError("out must have shape (%d, %d, %d)" % (ny, nx, nti))
+        check(self._L.mi_interp1_rows_f64_dev(self._ctx._h, self._h, C.c_void_p(Z.data_ptr()), zstride, ny * nx, _ptr(ti), nti,
+                                              C.c_void_p(out.data_ptr()), ostride, float(extrap)), self._ctx._h)
         return out
 
     def interp_cols_host(self, Y, xi, extrap=math.nan):

@@ -58,7 +58,8 @@ extern "C" {
  *                mi_interp1_each_f64_dev, mi_interp1_each_f64_host, mi_group_interp1_each_f64_host,
  *                mi_debug_each_launches (paired columns with a query vector per column, and a thin kernel for very
  *                short columns); mi_interp2_slices_f64_dev, mi_debug_slices2_launches (gridded interp2 over the slices of a
- *                cube, Z read in place; device form) */
+ *                cube, Z read in place; device form); mi_interp1_rows_f64_dev, mi_debug_rows1_launches (interp1 along
+ *                the rows of a matrix / across the slices of a cube: one X, a table per row; device form only) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -103,6 +104,9 @@ size_t mi_debug_each_launches(int form);
  * tile body, 1 LDS form with the flat body (thin outputs, nyi < 256), 2 direct form with the tile body, 3 direct form
  * with the flat body; 0 for any other value of form. */
 size_t mi_debug_slices2_launches(int form);
+/* Test hook: calls of mi_interp1_rows_f64_dev by this process so far that took the given form: 0 tile body with 16-B
+ * accesses, 1 tile body with 8-B accesses, 2 flat body (m < 256); 0 for any other value of form. */
+size_t mi_debug_rows1_launches(int form);
 /* Test hook: which closed form of the abscissae a mode-0 table evaluates (0 fma(i, dx, x0); 1 x0 + i*dx;
  * 2 x0 + span*(i/(n-1)); 3 the same with the quotient from a Markstein step) and whether its last node is pinned to
  * xmax -- i.e. which instance of the interp1 kernels a call on this table launches.  Both are -1 for the {x,y} modes. */
@@ -340,6 +344,34 @@ mi_status mi_interp2_slices_f64_dev(mi_ctx* ctx, const mi_axis1* ax, const mi_ax
                                     size_t z_slice_stride, size_t nslices, const double* xi_dev, size_t nxi,
                                     const double* yi_dev, size_t nyi, double* zi_dev, size_t ldzi, size_t zi_slice_stride,
                                     double extrap_val);
+
+/* ---- interp1 along the rows of a matrix / across the slices of a cube -------
+ * mi_interp1_cols_f64_dev for data stored the other way round: one table per ROW of a column-major matrix.  An ensemble
+ * stored realisation-fastest, one time level per contiguous block (the reference's [spike][realisation] arrays, index
+ * m*R + r); a stack of fields at n time levels, arma::cube(ny, nx, n).memptr(), interpolated to other times (m = ny*nx
+ * rows, ldy = the slice stride); a C-contiguous (n, B) "time-major" tensor.
+ *     y:  column-major m x n,   n = axis->n,  Y(r, k) = y[r + k*ldy],  ldy >= m,
+ *     yi: column-major m x nxi,               yi[r + i*ldyi],          ldyi >= m,
+ *     yi[r + i*ldyi] == what mi_interp1_f64_dev returns for xi[i] on the table (x, Y(r, :)) built without
+ *                       MI_GRID_SANITISE,  bit for bit:
+ * the fp64 blend at the top of this header, (1-w)*Y(r,l) + w*Y(r,rr) with rr = min(l+1, n-1), every operation rounded;
+ * extrap_val outside [x[0], x[n-1]]; NaN for a NaN query; Y(r, n-1) goes through the blend at x[n-1]; inf, NaN and -0.0
+ * inside a row go through the blend and never reach another row.  xi may be in any order.  Rows m..ldy-1 of every column
+ * of y never influence anything, rows m..ldyi-1 of yi are never written; yi must not overlap an input.
+ * Device form only: device pointers, 8-B aligned; asynchronous on the context's stream, no copy, no synchronisation; the
+ * only allocation grows the context's record workspace (nxi x 16 B, shared in stream order with mi_interp2_grid_f64_dev,
+ * mi_interp1_cols_f64_dev, mi_interp2_slices_f64_dev and the long-column forms of the paired-column calls); m == 0 or
+ * nxi == 0 is MI_OK with nothing launched or written.  Each query is located once per call; one kernel follows, in which
+ * a workgroup keeps the two bracketing columns of its 1024 rows in registers, so that with sorted xi every column of y a
+ * query brackets is read once and the others never; for m < 256 a flat kernel takes the record per output
+ * (csrc/mi_rows1.hip; mi_debug_rows1_launches tells which).  With xi in no order two columns are read per output.
+ * MI_ERR_INVALID_ARG for NULL or misaligned pointers, an axis of another device than the context's, ldy < m, ldyi < m,
+ * sizes whose byte counts overflow (ldy*n, ldyi*nxi, nxi*16).
+ * There is no host-pointer, group or arma:: form of this call.
+ * Which call when: one table per ROW, or interpolation across the slices of a cube -> this call; one table per column ->
+ * mi_interp1_cols_f64_dev; a single row with many queries (m == 1) -> mi_grid1 and mi_interp1_f64_dev. */
+mi_status mi_interp1_rows_f64_dev(mi_ctx* ctx, const mi_axis1* axis, const double* y_dev, size_t ldy, size_t m,
+                                  const double* xi_dev, size_t nxi, double* yi_dev, size_t ldyi, double extrap_val);
 
 /* ---- the reference's own interpolation ----------------------------------
  * Replaces RestrictKernel (EventDrivenMap.cu:769-785, launch :205-206):
