@@ -103,6 +103,7 @@ SIGNATURES = {
     "mi_group_size": (_i32, [_vp]),
     "mi_group_ctx": (_vp, [_vp, _i32]),
     "mi_group_synchronize": (_i32, [_vp]),
+    "mi_group_wait_stream": (_i32, [_vp, _i32, _vp]),
     "mi_shard_bounds": (None, [_sz, _i32, _i32, C.POINTER(_sz), C.POINTER(_sz)]),
     "mi_group_set_reduce": (_i32, [_vp, _i32]),
     "mi_group_rccl_ranks": (_i32, [_vp]),

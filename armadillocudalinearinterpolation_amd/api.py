@@ -980,6 +980,17 @@ class Group:
     def synchronize(self):
         check(self._L.mi_group_synchronize(self._h))
 
+    def wait_stream(self, rank, raw_stream):
+        """mi_group_wait_stream: member `rank`'s stream waits (on the device) for what `raw_stream` holds now"""
+        check(self._L.mi_group_wait_stream(self._h, int(rank), C.c_void_p(raw_stream)))
+
+    def _follow_torch(self):
+        """every member's stream behind torch's current stream of its device: tensors handed to the next call may still be
+        produced, or last written, there.  Stream-ordered (an event and a device-side wait per member), no host wait."""
+        torch = _torch()
+        for r, d in enumerate(self.devices):
+            self.wait_stream(r, torch.cuda.current_stream(d).cuda_stream)
+
     def grid1(self, X, Y, sanitise=True):
         X, Y = _np64(X), _np64(Y)
         t = C.c_void_p()
@@ -1064,7 +1075,10 @@ class GroupGrid1:
         """device-resident shards (one float64 tensor per group member, equal sizes); returns the per-shard results and,
         with gather=True, one buffer per member holding every shard (RCCL all-gather, or device copies in a rehearsal group).
         out / gathered: caller-owned result tensors (no allocation in the call); sync=False: return with the shards'
-        kernels enqueued on the members' streams (Group.synchronize waits) -- the shape bench.py --backend group times"""
+        kernels enqueued on the members' streams (Group.synchronize waits) -- the shape bench.py --backend group times.
+        Ordering: the members' streams are put behind torch's current stream of their device first, so the work that
+        produces xq_shards, or that last wrote out / gathered, may still be pending there when this is called.  With
+        sync=True the results are complete on return; with sync=False after Group.synchronize()."""
         torch = _torch()
         P, n = len(self._g), int(xq_shards[0].numel())
         assert len(xq_shards) == P and all(int(t.numel()) == n for t in xq_shards)
@@ -1076,6 +1090,7 @@ class GroupGrid1:
         if gather:
             assert len(full) == P and all(int(t.numel()) == P * n for t in full)
         arr = lambda ts: (C.c_void_p * P)(*[t.data_ptr() for t in ts])  # noqa: E731
+        self._g._follow_torch()
         check(self._L.mi_group_interp1_f64_dev(self._g._h, self._h, arr(xq_shards), arr(outs), n, float(extrap),
                                                arr(full) if gather else None))
         if sync:
@@ -1116,7 +1131,9 @@ class GroupGrid2:
         return out.T
 
     def interp_dev(self, xq_shards, yq_shards, extrap=math.nan, gather=False):
-        """device-resident shards (one pair of float64 tensors per group member, equal sizes)"""
+        """device-resident shards (one pair of float64 tensors per group member, equal sizes).  The members' streams are put
+        behind torch's current stream of their device first (the shards' producers may still be pending there); the
+        results are complete on return."""
         torch = _torch()
         P, n = len(self._g), int(xq_shards[0].numel())
         assert len(xq_shards) == P and len(yq_shards) == P
@@ -1124,6 +1141,7 @@ class GroupGrid2:
         outs = [torch.empty_like(t) for t in xq_shards]
         full = [torch.empty(P * n, dtype=torch.float64, device=t.device) for t in xq_shards] if gather else None
         arr = lambda ts: (C.c_void_p * P)(*[t.data_ptr() for t in ts])  # noqa: E731
+        self._g._follow_torch()
         check(self._L.mi_group_interp2_f64_dev(self._g._h, self._h, arr(xq_shards), arr(yq_shards), arr(outs), n,
                                                float(extrap), arr(full) if gather else None))
         self._g.synchronize()

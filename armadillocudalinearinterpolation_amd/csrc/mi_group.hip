@@ -29,6 +29,9 @@ struct mi_group {
     std::vector<int> dev;
     std::vector<mi_ctx*> ctx;
     std::vector<hipEvent_t> done;      // per shard: its kernels of the current call have been enqueued up to here
+    // created on first use (a group that never takes device-resident shards never has them):
+    std::vector<hipEvent_t> pre;       // per shard: the caller's stream has been enqueued up to here (mi_group_wait_stream)
+    std::vector<hipEvent_t> copied;    // per shard, repeated devices: its gather copies have been enqueued up to here
     bool distinct = true;
     int reduce_mode = 0;
     // RCCL, bound lazily
@@ -105,6 +108,15 @@ mi_status bind_rccl(mi_group* g)
         return mi::fail(nullptr, MI_ERR_HIP, "ncclCommInitAll over %zu devices failed: %s", g->dev.size(),
                         g->GetErrorString ? g->GetErrorString(r) : "?");
     }
+    return MI_OK;
+}
+
+// member r's event of a per-member vector that is filled on first use (the device of member r is current)
+mi_status member_event(mi_group* g, std::vector<hipEvent_t>& v, size_t r, hipEvent_t* out)
+{
+    if (v.size() != g->ctx.size()) v.assign(g->ctx.size(), nullptr);
+    if (!v[r]) MI_HIP(g->ctx[r], hipEventCreateWithFlags(&v[r], hipEventDisableTiming));
+    *out = v[r];
     return MI_OK;
 }
 
@@ -185,6 +197,8 @@ mi_status mi_group_destroy(mi_group* g)
         (void)hipSetDevice(g->dev[r]);
         if (r < g->red_dev.size() && g->red_dev[r]) (void)hipFree(g->red_dev[r]);
         if (g->done[r]) (void)hipEventDestroy(g->done[r]);
+        if (r < g->pre.size() && g->pre[r]) (void)hipEventDestroy(g->pre[r]);
+        if (r < g->copied.size() && g->copied[r]) (void)hipEventDestroy(g->copied[r]);
         if (r < g->gstream.size() && g->gstream[r]) (void)hipStreamDestroy(g->gstream[r]);
         if (r < g->gdone.size() && g->gdone[r]) (void)hipEventDestroy(g->gdone[r]);
         if (r < g->cdone.size())
@@ -243,6 +257,26 @@ mi_status mi_group_synchronize(mi_group* g)
         mi_status st = mi_ctx_synchronize(g->ctx[r]);
         if (st != MI_OK) return st;
     }
+    return MI_OK;
+}
+
+mi_status mi_group_wait_stream(mi_group* g, int rank, void* stream)
+{
+    MI_REQUIRE(nullptr, g != nullptr, "mi_group_wait_stream: group is NULL");
+    MI_REQUIRE(nullptr, rank >= 0 && rank < (int)g->ctx.size(), "mi_group_wait_stream: rank=%d not in [0,%zu)", rank, g->ctx.size());
+    // stream-ordered, no host wait: an event on the caller's stream (NULL: the device's default stream), and the member's
+    // stream behind it.  The exchange stream of the chunked gather starts behind the member's stream, so it is covered.
+    mi_ctx* c = g->ctx[rank];
+    MI_HIP(c, hipSetDevice(g->dev[rank]));
+    // nothing pending there (the timed loop of bench.py --backend group): nothing to order behind, and the member's queue
+    // is spared a barrier per call.  hipStreamQuery does not wait; any answer but "idle" takes the ordered path.
+    if (hipStreamQuery((hipStream_t)stream) == hipSuccess) return MI_OK;
+    (void)hipGetLastError();   // hipErrorNotReady is an answer, not a failure
+    hipEvent_t pre = nullptr;
+    const mi_status st = member_event(g, g->pre, (size_t)rank, &pre);
+    if (st != MI_OK) return st;
+    MI_HIP(c, hipEventRecord(pre, (hipStream_t)stream));
+    MI_HIP(c, hipStreamWaitEvent(c->stream, pre, 0));
     return MI_OK;
 }
 
@@ -399,7 +433,16 @@ static mi_status gather_shards(mi_group* g, double* const* part_dev, double* con
             MI_HIP(g->ctx[r], hipStreamWaitEvent(g->ctx[r]->stream, g->done[s], 0));
             MI_HIP(g->ctx[r], hipMemcpyAsync(dst, part_dev[s], n_per_shard * sizeof(double), hipMemcpyDeviceToDevice, g->ctx[r]->stream));
         }
+        hipEvent_t copied = nullptr;
+        const mi_status st = member_event(g, g->copied, r, &copied);
+        if (st != MI_OK) return st;
+        MI_HIP(g->ctx[r], hipEventRecord(copied, g->ctx[r]->stream));
     }
+    // member r's copies read every other member's part_dev[s]: member s's stream ends behind them, so that a later call
+    // that writes part_dev[s] again is ordered behind the reads without a synchronisation in between
+    for (size_t s = 0; s < P; ++s)
+        for (size_t r = 0; r < P; ++r)
+            if (r != s) MI_HIP(g->ctx[s], hipStreamWaitEvent(g->ctx[s]->stream, g->copied[r], 0));
     return MI_OK;
 }
 
@@ -481,6 +524,12 @@ static mi_status interp1_chunked_gather(mi_group* g, const mi_group_grid1* t, co
         MI_HIP(g->ctx[r], hipEventRecord(g->gdone[r], g->gstream[r]));
         MI_HIP(g->ctx[r], hipStreamWaitEvent(g->ctx[r]->stream, g->gdone[r], 0));
     }
+    // repeated devices: member r's exchange stream copied out of every other member's yq_dev[s], so member s's stream ends
+    // behind those reads too (with RCCL the broadcasts of member s's own communicator rank are what reads its buffer)
+    if (!g->distinct)
+        for (size_t s = 0; s < P; ++s)
+            for (size_t r = 0; r < P; ++r)
+                if (r != s) MI_HIP(g->ctx[s], hipStreamWaitEvent(g->ctx[s]->stream, g->gdone[r], 0));
     return MI_OK;
 }
 

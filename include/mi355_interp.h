@@ -59,7 +59,8 @@ extern "C" {
  *                mi_debug_each_launches (paired columns with a query vector per column, and a thin kernel for very
  *                short columns); mi_interp2_slices_f64_dev, mi_debug_slices2_launches (gridded interp2 over the slices of a
  *                cube, Z read in place; device form); mi_interp1_rows_f64_dev, mi_debug_rows1_launches (interp1 along
- *                the rows of a matrix / across the slices of a cube: one X, a table per row; device form only) */
+ *                the rows of a matrix / across the slices of a cube: one X, a table per row; device form only);
+ *                mi_group_wait_stream (a group member's stream behind a stream of the caller's) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -548,6 +549,13 @@ mi_status mi_group_destroy(mi_group* g);
 int mi_group_size(const mi_group* g);
 mi_ctx* mi_group_ctx(mi_group* g, int rank);          /* shard `rank`'s context (owned by the group) */
 mi_status mi_group_synchronize(mi_group* g);
+/* Member `rank`'s stream waits for the work that `stream` (a hipStream_t of that member's device; NULL: its default stream)
+ * holds at the time of the call: an event recorded there, waited for on the device -- the host does not wait (and a
+ * stream that is idle at the call costs one hipStreamQuery, no event).  This is how
+ * a caller orders the producers of the buffers it hands to mi_group_interp1_f64_dev / mi_group_interp2_f64_dev (and the
+ * last writers of the result buffers) in front of the group's kernels; the Python interp_dev forms call it with torch's
+ * current stream of every member's device. */
+mi_status mi_group_wait_stream(mi_group* g, int rank, void* stream);
 /* contiguous, balanced split of n units over `world` shards: shard `rank` = [lo, hi); the first n % world shards get
  * one extra unit.  Host arithmetic only. */
 void mi_shard_bounds(size_t n, int rank, int world, size_t* lo, size_t* hi);
@@ -572,7 +580,9 @@ mi_status mi_group_interp1_f64_host(mi_group* g, const mi_group_grid1* t, const 
 /* Device-resident shards: xq_dev[r] / yq_dev[r] point to nq_per_shard doubles on device r.  Asynchronous (each shard on
  * its context's stream; mi_group_synchronize waits).  gathered_dev (optional, may be NULL): gathered_dev[r] is a buffer
  * of P * nq_per_shard doubles on device r that receives EVERY shard's results (shard s at offset s * nq_per_shard;
- * in place when yq_dev[r] == gathered_dev[r] + r * nq_per_shard): an RCCL all-gather over xGMI behind the kernels. */
+ * in place when yq_dev[r] == gathered_dev[r] + r * nq_per_shard): an RCCL all-gather over xGMI behind the kernels.
+ * The members' streams are not ordered behind any other stream: a C caller orders its own producers with
+ * mi_group_wait_stream.  Calls on one group are ordered among themselves, gathers included. */
 mi_status mi_group_interp1_f64_dev(mi_group* g, const mi_group_grid1* t, const double* const* xq_dev,
                                    double* const* yq_dev, size_t nq_per_shard, double extrap_val,
                                    double* const* gathered_dev);

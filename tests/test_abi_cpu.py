@@ -76,7 +76,8 @@ def test_public_header_is_plain_c99(tmp_path):
                    "  (fn)mi_group_grid1_destroy, (fn)mi_group_interp1_f64_host, (fn)mi_group_interp1_f64_dev,\n"
                    "  (fn)mi_group_grid2_create, (fn)mi_group_grid2_destroy, (fn)mi_group_interp2_f64_host, (fn)mi_group_interp2_f64_dev,\n"
                    "  (fn)mi_group_edm_create, (fn)mi_group_edm_destroy, (fn)mi_group_edm_set_params,\n"
-                   "  (fn)mi_group_edm_compute_f, (fn)mi_group_edm_shard, (fn)mi_group_edm_shard_bounds };\n"
+                   "  (fn)mi_group_edm_compute_f, (fn)mi_group_edm_shard, (fn)mi_group_edm_shard_bounds,\n"
+                   "  (fn)mi_group_set_gather_chunks, (fn)mi_group_wait_stream };\n"
                    "int main(void) { mi_edm_params p; size_t lo, hi; double z[3] = {0.3, 0.7, 1.4}, f[3], sc[MI_EDM_PARTIAL_LEN(3)] = {3, 3, 3, 2, 9, 9, 9};\n"
                    "  mi_edm_default_params(&p); mi_shard_bounds(10, 1, 3, &lo, &hi);      /* host-only calls really run */\n"
                    "  if (mi_edm_residual_from_sums(&p, z, sc, f) != MI_OK) return 2;\n"
@@ -107,6 +108,15 @@ def test_shard_bounds_host_arithmetic():
             assert b[0][0] == 0 and b[-1][1] == n and all(b[i][1] == b[i + 1][0] for i in range(world - 1))
             sizes = [h - l for l, h in b]
             assert max(sizes) - min(sizes) <= 1
+
+
+def test_group_wait_stream_checks_its_arguments_before_any_device_call():
+    """mi_group_wait_stream (additive in ABI 4) is bound with (group, rank, stream) and rejects a NULL group with
+    MI_ERR_INVALID_ARG and its own name in the thread's last error -- before it touches a device, so this runs anywhere."""
+    assert _lib.SIGNATURES["mi_group_wait_stream"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+    L = _lib.load()
+    assert L.mi_group_wait_stream(None, 0, None) == 1
+    assert "mi_group_wait_stream" in L.mi_last_error(None).decode()
 
 
 def test_no_product_kernel_uses_scratch(tmp_path):
