@@ -42,6 +42,104 @@ def _np64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
 
 
+class _Handle:
+    """Owner of one handle of the C ABI: _L the library, _h the handle, _destroy the name of the function that frees it.
+    Context, Grid1 and Grid2 do not derive from it yet and keep the same lines of their own (DESIGN.md section 1 says why)."""
+    _destroy = None
+
+    def _own(self, L, h, ctx=None):
+        """take handle h; one created on a Context is also closed when that context is, before it (its device state
+        belongs to the context).  A group member's context (_GroupCtx) keeps no such list: the group owns it."""
+        self._L, self._h = L, h
+        if hasattr(ctx, "_children"):
+            ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _need_f64_cuda(t, what, contiguous, message=None):
+    """ValueError unless t is a float64 CUDA tensor (and contiguous, if asked); message: a call site's own wording"""
+    if not (t.is_cuda and t.dtype == _torch().float64 and (not contiguous or t.is_contiguous())):
+        raise ValueError(message or "%s must be a %sfloat64 CUDA tensor" % (what, "contiguous " if contiguous else ""))
+
+
+def _strides(a):
+    """strides of a tensor or numpy array, in elements"""
+    return a.stride() if hasattr(a, "stride") else tuple(s // a.itemsize for s in a.strides)
+
+
+def _leading_dim(a, rows, cols):
+    """Leading dimension of the column-major (rows, cols) matrix in the first two dimensions of a -- element (i, j) at
+    i + j*ld -- or None if a is not laid out so: rows not adjacent, or columns that overlap.  The stride of a single
+    column is not read (it means nothing): such a matrix is dense."""
+    st = _strides(a)
+    ld = st[1] if cols > 1 else max(rows, 1)
+    return None if (rows > 1 and st[0] != 1) or ld < rows else ld
+
+
+def _cube_view(a, rows, cols, what):
+    """(leading dimension, slice stride, slices) of a 3-D (rows, cols, S) array or tensor stored like an arma::cube:
+    element (i, j, s) at i + j*ld + s*stride, i.e. the .permute(2, 1, 0) view of a contiguous (S, cols, rows) buffer, or
+    a padded view of one; strides in elements"""
+    shape = tuple(a.shape)
+    if len(shape) != 3 or shape[0] != rows or shape[1] != cols:
+        raise ValueError("%s must have shape (%d, %d, S)" % (what, rows, cols))
+    S = shape[2]
+    ld = _leading_dim(a, rows, cols)
+    stride = _strides(a)[2] if S > 1 else (ld or 0) * cols           # the stride of a single slice is not read either
+    if ld is None or stride < ld * cols:
+        raise ValueError("%s must be stored slice by slice, column-major inside a slice (the .permute(2, 1, 0) view of a "
+                         "contiguous (S, %d, %d) buffer)" % (what, cols, rows))
+    return ld, stride, S
+
+
+# Result buffers: the one the call allocates by default, or the caller's `out` once it passed the same rules.
+
+def _out_colmajor(out, rows, B, Y):
+    """(out, leading dimension) of a column-major (rows, B) result beside Y's B columns; default: the .T view of a new
+    contiguous (B, rows) buffer"""
+    if out is None:
+        out = _torch().empty((B, rows), dtype=_torch().float64, device=Y.device).T
+    else:
+        _need_f64_cuda(out, "out", False)
+    ld, Bo = Axis1._colmajor_view(out, rows, "out")
+    if Bo != B:
+        raise ValueError("out must have as many columns as Y")
+    return out, ld
+
+
+def _out_rows(out, m, cols, Y):
+    """(out, leading dimension) of a column-major (m, cols) result beside Y's m row tables; default: the .T view of a
+    new contiguous (cols, m) buffer"""
+    if out is None:
+        out = _torch().empty((cols, m), dtype=_torch().float64, device=Y.device).T
+    else:
+        _need_f64_cuda(out, "out", False)
+    ld, mo = Axis1._rows_view(out, cols, "out")
+    if mo != m:
+        raise ValueError("out must have as many rows as Y")
+    return out, ld
+
+
+def _out_cube(out, rows, cols, S, Z):
+    """a (rows, cols, S) result laid out like an arma::cube beside Z; default: the .permute(2, 1, 0) view of a new
+    contiguous (S, cols, rows) buffer.  The caller checks the layout: interp_stack wants dense slices, interp2_slices
+    takes padded ones."""
+    if out is None:
+        return _torch().empty((S, cols, rows), dtype=_torch().float64, device=Z.device).permute(2, 1, 0)
+    _need_f64_cuda(out, "out", False)
+    return out
+
+
 class Context:
     """mi_ctx: one device + one stream.  By default it follows torch's current stream."""
 
@@ -102,15 +200,15 @@ class Context:
             pass
 
 
-class Timer:
+class Timer(_Handle):
     """HIP events recorded on the context's stream."""
+    _destroy = "mi_timer_destroy"
 
     def __init__(self, ctx):
         self._ctx = ctx
-        self._L = ctx._L
         h = C.c_void_p()
-        check(self._L.mi_timer_create(ctx._h, C.byref(h)), ctx._h)
-        self._h = h
+        check(ctx._L.mi_timer_create(ctx._h, C.byref(h)), ctx._h)
+        self._own(ctx._L, h)
 
     def start(self):
         check(self._L.mi_timer_start(self._h), self._ctx._h)
@@ -122,17 +220,6 @@ class Timer:
         ms = C.c_float(0)
         check(self._L.mi_timer_elapsed_ms(self._h, C.byref(ms)), self._ctx._h)
         return float(ms.value)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mi_timer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Grid1:
@@ -279,6 +366,8 @@ class Grid2:
             raise ValueError("xq and yq must have the same number of elements")
         if out is None:
             out = torch.empty_like(xq)
+        elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == xq.numel()):
+            raise ValueError("out must be a contiguous float64 CUDA tensor of the same size")     # Grid1.interp's rule
         check(self._L.mi_interp2_f64_dev(self._ctx._h, self._h, _ptr(xq), _ptr(yq), _ptr(out), xq.numel(),
                                          float(extrap)), self._ctx._h)
         return out
@@ -327,7 +416,7 @@ class Grid2:
             pass
 
 
-class Axis1:
+class Axis1(_Handle):
     """Validated, device-resident 1-D axis (mi_axis1) for interp1 over the columns of a matrix: one X, many Y.
 
     Layout, as arma::mat: Y is (n, B) with one profile per COLUMN, stored column-major -- element (i, c) at
@@ -340,10 +429,11 @@ class Axis1:
     at n time levels through interp_stack (interpolation along the slice index); both are one call of
     mi_interp1_rows_f64_dev and bit-identical to interp_cols on the transposed data.  Device tensors only."""
 
+    _destroy = "mi_axis1_destroy"
+
     def __init__(self, ctx, handle, n):
-        self._ctx, self._h, self._L, self.n = ctx, handle, ctx._L, int(n)
-        if hasattr(ctx, "_children"):
-            ctx._children.add(self)
+        self._ctx, self.n = ctx, int(n)
+        self._own(ctx._L, handle, ctx)
 
     @classmethod
     def from_nodes(cls, ctx, x):
@@ -372,31 +462,20 @@ class Axis1:
         shape = tuple(a.shape)
         if len(shape) != 2 or shape[0] != rows:
             raise ValueError("%s must have shape (%d, B)" % (what, rows))
-        st = a.stride() if hasattr(a, "stride") else tuple(s // a.itemsize for s in a.strides)
-        B = shape[1]
-        ld = st[1] if B > 1 else max(rows, 1)
-        if (rows > 1 and st[0] != 1) or ld < rows:
+        ld = _leading_dim(a, rows, shape[1])
+        if ld is None:
             raise ValueError("%s must be column-major (the .T view of a contiguous (B, %d) buffer)" % (what, rows))
-        return ld, B
+        return ld, shape[1]
 
     def interp_cols(self, Y, xi, out=None, extrap=math.nan):
         """Y: (n, B) float64 CUDA tensor, column-major (see the class docstring); xi: contiguous float64 CUDA tensor of
         nxi queries in any order; out: column-major (nxi, B) tensor (default: the .T view of a new contiguous (B, nxi)
         buffer).  Returns the (nxi, B) result; asynchronous on the context's stream."""
-        torch = _torch()
-        if not (xi.is_cuda and xi.dtype == torch.float64 and xi.is_contiguous()):
-            raise ValueError("xi must be a contiguous float64 CUDA tensor")
-        if not (Y.is_cuda and Y.dtype == torch.float64):
-            raise ValueError("Y must be a float64 CUDA tensor")
+        _need_f64_cuda(xi, "xi", True)
+        _need_f64_cuda(Y, "Y", False)
         ldy, B = self._colmajor_view(Y, self.n, "Y")
         nxi = xi.numel()
-        if out is None:
-            out = torch.empty((B, nxi), dtype=torch.float64, device=Y.device).T
-        elif not (out.is_cuda and out.dtype == torch.float64):
-            raise ValueError("out must be a float64 CUDA tensor")
-        ldyi, Bo = self._colmajor_view(out, nxi, "out")
-        if Bo != B:
-            raise ValueError("out must have as many columns as Y")
+        out, ldyi = _out_colmajor(out, nxi, B, Y)
         check(self._L.mi_interp1_cols_f64_dev(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, B, _ptr(xi), nxi,
                                               C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
         return out
@@ -409,12 +488,10 @@ class Axis1:
         shape = tuple(a.shape)
         if len(shape) != 2 or shape[1] != cols:
             raise ValueError("%s must have shape (m, %d)" % (what, cols))
-        st = a.stride() if hasattr(a, "stride") else tuple(s // a.itemsize for s in a.strides)
-        m = shape[0]
-        ld = st[1] if cols > 1 else max(m, 1)
-        if (m > 1 and st[0] != 1) or ld < m:
+        ld = _leading_dim(a, shape[0], cols)
+        if ld is None:
             raise ValueError("%s must be column-major (the .T view of a contiguous (%d, m) buffer)" % (what, cols))
-        return ld, m
+        return ld, shape[0]
 
     @staticmethod
     def _stack_view(a, what):
@@ -436,20 +513,11 @@ class Axis1:
         order; out: (m, nxi) tensor in the same layout (default: the .T view of a new contiguous (nxi, m) buffer).
         Returns out with out[r, i] = interp1 of xi[i] on (X, Y[r, :]), bit-identical to interp_cols on the transposed
         data; asynchronous on the context's stream."""
-        torch = _torch()
         ldy, m = self._rows_view(Y, self.n, "Y")
-        if not (xi.is_cuda and xi.dtype == torch.float64 and xi.is_contiguous()):
-            raise ValueError("xi must be a contiguous float64 CUDA tensor")
-        if not (Y.is_cuda and Y.dtype == torch.float64):
-            raise ValueError("Y must be a float64 CUDA tensor")
+        _need_f64_cuda(xi, "xi", True)
+        _need_f64_cuda(Y, "Y", False)
         nxi = xi.numel()
-        if out is None:
-            out = torch.empty((nxi, m), dtype=torch.float64, device=Y.device).T
-        elif not (out.is_cuda and out.dtype == torch.float64):
-            raise ValueError("out must be a float64 CUDA tensor")
-        ldyi, mo = self._rows_view(out, nxi, "out")
-        if mo != m:
-            raise ValueError("out must have as many rows as Y")
+        out, ldyi = _out_rows(out, m, nxi, Y)
         check(self._L.mi_interp1_rows_f64_dev(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, m, _ptr(xi), nxi,
                                               C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
         return out
@@ -460,19 +528,13 @@ class Axis1:
         stride may exceed ny*nx); ti: contiguous float64 CUDA tensor of nti times in any order; out: (ny, nx, nti) tensor
         of the same layout (default: the .permute(2, 1, 0) view of a new contiguous (nti, nx, ny) buffer).  Returns out
         with out[i, j, k] = interp1 of ti[k] on (X, Z[i, j, :]): one call of mi_interp1_rows_f64_dev with m = ny*nx."""
-        torch = _torch()
         ny, nx, zstride, S = self._stack_view(Z, "Z")
         if S != self.n:
             raise ValueError("Z must hold one slice per node of the axis (%d), not %d" % (self.n, S))
-        if not (ti.is_cuda and ti.dtype == torch.float64 and ti.is_contiguous()):
-            raise ValueError("ti must be a contiguous float64 CUDA tensor")
-        if not (Z.is_cuda and Z.dtype == torch.float64):
-            raise ValueError("Z must be a float64 CUDA tensor")
+        _need_f64_cuda(ti, "ti", True)
+        _need_f64_cuda(Z, "Z", False)
         nti = ti.numel()
-        if out is None:
-            out = torch.empty((nti, nx, ny), dtype=torch.float64, device=Z.device).permute(2, 1, 0)
-        elif not (out.is_cuda and out.dtype == torch.float64):
-            raise ValueError("out must be a float64 CUDA tensor")
+        out = _out_cube(out, ny, nx, nti, Z)
         oy, ox, ostride, So = self._stack_view(out, "out")
         if (oy, ox, So) != (ny, nx, nti):
             raise ValueError("out must have shape (%d, %d, %d)" % (ny, nx, nti))
@@ -483,28 +545,183 @@ class Axis1:
     def interp_cols_host(self, Y, xi, extrap=math.nan):
         """host form: Y a (n, B) numpy array (any layout; a column-major one is used in place), xi numpy queries;
         returns a Fortran-ordered (nxi, B) array (synchronous)"""
-        xi = _np64(xi)
-        Y = np.asarray(Y, dtype=np.float64)
-        if Y.ndim != 2 or Y.shape[0] != self.n:
-            raise ValueError("Y must have shape (%d, B)" % self.n)
-        if not Y.flags["F_CONTIGUOUS"]:
-            Y = np.asfortranarray(Y)
-        B = Y.shape[1]
-        out = np.empty((B, xi.size)).T
-        check(self._L.mi_interp1_cols_f64_host(self._ctx._h, self._h, C.c_void_p(Y.ctypes.data), self.n, B, _ptr(xi), xi.size,
-                                               C.c_void_p(out.ctypes.data), xi.size, float(extrap)), self._ctx._h)
-        return out
+        return _cols_host(self._L, "mi_interp1_cols_f64_host", (self._ctx._h, self._h), self.n, "%d" % self.n, Y, xi, extrap,
+                          self._ctx._h)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mi_axis1_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _cols_host(L, fn, table, n, n_words, Y, xi, extrap, ctx_h=None):
+    """The host form of interp1 over the columns of Y, for a context and for a group: fn names the C function of library
+    L (looked up once the arguments have passed: the rules need no library), table holds its leading arguments, (ctx,
+    axis) or (group, X, n); n_words says n in the shape message; ctx_h is the context a failure is reported on."""
+    xi = _np64(xi)
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim != 2 or Y.shape[0] != n:
+        raise ValueError("Y must have shape (%s, B)" % n_words)
+    if not Y.flags["F_CONTIGUOUS"]:
+        Y = np.asfortranarray(Y)
+    B = Y.shape[1]
+    out = np.empty((B, xi.size)).T
+    check(getattr(L, fn)(*table, C.c_void_p(Y.ctypes.data), n, B, _ptr(xi), xi.size, C.c_void_p(out.ctypes.data), xi.size,
+             float(extrap)), ctx_h)
+    return out
+
+
+# ---- interp1 over paired columns, and interp2 over the slices of a cube -------------------------------------------
+
+def _paired_args(X, Y, queries, lens, out, want_ok):
+    """What interp_pairs and interp_each share, checked in the order both keep: X and Y, then the queries -- the one
+    step that differs: queries(B) returns (nxi, ldxi) -- then lens, out and ok.
+    Returns (n, B, ldx, ldy, nxi, ldxi, out, ldyi, ok)."""
+    torch = _torch()
+    for t in (X, Y):
+        _need_f64_cuda(t, "X and Y", False, "X and Y must be float64 CUDA tensors")
+    if X.dim() != 2 or tuple(X.shape) != tuple(Y.shape):
+        raise ValueError("X and Y must both have shape (n, B)")
+    n = int(X.shape[0])
+    ldx, B = Axis1._colmajor_view(X, n, "X")
+    ldy, _ = Axis1._colmajor_view(Y, n, "Y")
+    nxi, ldxi = queries(B)
+    if lens is not None and not (lens.is_cuda and lens.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                 and lens.is_contiguous() and tuple(lens.shape) == (B,)):
+        raise ValueError("lens must be a contiguous int32 CUDA tensor of shape (B,)")
+    out, ldyi = _out_colmajor(out, nxi, B, Y)
+    ok = torch.empty((B,), dtype=torch.int32, device=Y.device) if want_ok else None
+    return n, B, ldx, ldy, nxi, ldxi, out, ldyi, ok
+
+
+def interp_pairs(ctx, X, Y, xi, lens=None, out=None, extrap=math.nan, want_ok=False):
+    """interp1 over paired columns (mi_interp1_pairs_f64_dev): column c of Y is sampled at the nodes in column c of X.
+
+    X, Y: (n, B) float64 CUDA tensors given as column-major views (Axis1's layout rules: the .T view of a contiguous
+    (B, ld) buffer; X and Y may have different leading dimensions); xi: contiguous float64 CUDA tensor of nxi queries in
+    any order, shared by every column; lens: optional contiguous (B,) int32 / uint32 CUDA tensor, the number of valid
+    leading rows of each column; out: column-major (nxi, B) tensor (default: the .T view of a new contiguous (B, nxi)
+    buffer).  X is validated on the device at every call: a column whose length is outside [2, n] or whose nodes are not
+    finite and strictly increasing gives NaN in all its outputs.  Returns the (nxi, B) result, or (result, ok) with
+    want_ok=True, ok a (B,) int32 CUDA tensor (1 good, 0 bad).  Asynchronous on the context's stream."""
+    _need_f64_cuda(xi, "xi", True)
+    n, B, ldx, ldy, nxi, _, out, ldyi, ok = _paired_args(X, Y, lambda B: (xi.numel(), 0), lens, out, want_ok)
+    check(ctx._L.mi_interp1_pairs_f64_dev(ctx._h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, n,
+                                          C.c_void_p(lens.data_ptr()) if lens is not None else None, B, _ptr(xi), nxi,
+                                          C.c_void_p(out.data_ptr()), ldyi, float(extrap),
+                                          C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
+    return (out, ok) if want_ok else out
+
+
+def _pairs_host_args(X, Y, xi, lens):
+    xi = _np64(xi)
+    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    if X.ndim != 2 or X.shape != Y.shape:
+        raise ValueError("X and Y must both have shape (n, B)")
+    X = X if X.flags["F_CONTIGUOUS"] else np.asfortranarray(X)
+    Y = Y if Y.flags["F_CONTIGUOUS"] else np.asfortranarray(Y)
+    n, B = X.shape
+    if lens is not None:
+        lens = np.ascontiguousarray(np.asarray(lens).reshape(-1).astype(np.uint32, casting="unsafe"))
+        if lens.size != B:
+            raise ValueError("lens must hold one count per column")
+    return X, Y, xi, lens, n, B
+
+
+def _pairs_host(L, fn, h, X, Y, xi, lens, extrap, want_ok, ctx_h=None):
+    """interp_pairs_host for a context and for a group: fn names the C function of library L (looked up once the
+    arguments have passed), h is its context or group handle, ctx_h the context a failure is reported on"""
+    X, Y, xi, lens, n, B = _pairs_host_args(X, Y, xi, lens)
+    out = np.empty((B, xi.size)).T
+    ok = np.ones(B, dtype=np.uint32) if want_ok else None
+    check(getattr(L, fn)(h, C.c_void_p(X.ctypes.data), max(n, 1), C.c_void_p(Y.ctypes.data), max(n, 1), n,
+             _ptr(lens) if lens is not None else None, B, _ptr(xi), xi.size, C.c_void_p(out.ctypes.data), max(xi.size, 1),
+             float(extrap), _ptr(ok) if want_ok else None), ctx_h)
+    return (out, ok) if want_ok else out
+
+
+def interp_pairs_host(ctx, X, Y, xi, lens=None, extrap=math.nan, want_ok=False):
+    """host form of interp_pairs (mi_interp1_pairs_f64_host): (n, B) numpy arrays (any layout; column-major ones are
+    used in place), numpy queries and counts; returns a Fortran-ordered (nxi, B) array, or (array, ok) with want_ok=True
+    (ok: (B,) uint32).  Synchronous.  Without want_ok a bad column raises MiError (code 2, MI_ERR_GRID)."""
+    return _pairs_host(ctx._L, "mi_interp1_pairs_f64_host", ctx._h, X, Y, xi, lens, extrap, want_ok, ctx._h)
+
+
+def interp_each(ctx, X, Y, XI, lens=None, out=None, extrap=math.nan, want_ok=False):
+    """interp1 over paired columns with a query vector per column (mi_interp1_each_f64_dev): column c of Y, sampled at
+    the nodes in column c of X, is evaluated at the queries in column c of XI.
+
+    X, Y, lens, out, the validation of X and the return value are interp_pairs'.  XI is either a column-major (nxi, B)
+    float64 CUDA view (Axis1's layout rules; its own leading dimension): the queries of each column -- or a contiguous
+    1-D float64 CUDA tensor of nxi queries shared by every column (ldxi = 0): bit-identical to interp_pairs, and served by
+    the thin one-lane-per-column kernel when the columns are very short.  Asynchronous on the context's stream."""
+    def queries(B):
+        if XI.dim() == 1:
+            if not XI.is_contiguous():
+                raise ValueError("a shared XI must be a contiguous 1-D tensor")
+            return XI.numel(), 0
+        if XI.dim() != 2:
+            raise ValueError("XI must be a column-major (nxi, B) view or a contiguous 1-D tensor")
+        nxi = int(XI.shape[0])
+        ldxi, Bq = Axis1._colmajor_view(XI, nxi, "XI")
+        if Bq != B:
+            raise ValueError("XI must have as many columns as X")
+        return nxi, ldxi
+
+    _need_f64_cuda(XI, "XI", False)
+    n, B, ldx, ldy, nxi, ldxi, out, ldyi, ok = _paired_args(X, Y, queries, lens, out, want_ok)
+    check(ctx._L.mi_interp1_each_f64_dev(ctx._h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, n,
+                                         C.c_void_p(lens.data_ptr()) if lens is not None else None, B,
+                                         C.c_void_p(XI.data_ptr()), ldxi, nxi, C.c_void_p(out.data_ptr()), ldyi, float(extrap),
+                                         C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
+    return (out, ok) if want_ok else out
+
+
+def _each_host_args(X, Y, XI, lens):
+    """the host forms' arguments: (X, Y, XI, lens, n, B, nxi, ldxi); a 2-D XI must be (nxi, B), a 1-D one is shared"""
+    XI = np.asarray(XI, dtype=np.float64)
+    if XI.ndim == 1:
+        X, Y, xi, lens, n, B = _pairs_host_args(X, Y, XI, lens)
+        return X, Y, xi, lens, n, B, xi.size, 0
+    X, Y, _, lens, n, B = _pairs_host_args(X, Y, np.zeros(0), lens)
+    if XI.ndim != 2 or XI.shape[1] != B:
+        raise ValueError("XI must have shape (nxi, B), one column of queries per column of X, or be 1-D")
+    XI = XI if XI.flags["F_CONTIGUOUS"] else np.asfortranarray(XI)
+    return X, Y, XI, lens, n, B, XI.shape[0], max(XI.shape[0], 1)
+
+
+def _each_host(L, fn, h, X, Y, XI, lens, extrap, want_ok, ctx_h=None):
+    """interp_each_host for a context and for a group; the arguments of _pairs_host"""
+    X, Y, XI, lens, n, B, nxi, ldxi = _each_host_args(X, Y, XI, lens)
+    out = np.empty((B, nxi)).T
+    ok = np.ones(B, dtype=np.uint32) if want_ok else None
+    check(getattr(L, fn)(h, C.c_void_p(X.ctypes.data), max(n, 1), C.c_void_p(Y.ctypes.data), max(n, 1), n,
+             _ptr(lens) if lens is not None else None, B, C.c_void_p(XI.ctypes.data), ldxi, nxi,
+             C.c_void_p(out.ctypes.data), max(nxi, 1), float(extrap), _ptr(ok) if want_ok else None), ctx_h)
+    return (out, ok) if want_ok else out
+
+
+def interp_each_host(ctx, X, Y, XI, lens=None, extrap=math.nan, want_ok=False):
+    """host form of interp_each (mi_interp1_each_f64_host): (n, B) numpy arrays, XI an (nxi, B) array (any layout;
+    column-major ones are used in place) or a 1-D array shared by every column; returns a Fortran-ordered (nxi, B) array,
+    or (array, ok) with want_ok=True.  Synchronous.  Without want_ok a bad column raises MiError (code 2, MI_ERR_GRID)."""
+    return _each_host(ctx._L, "mi_interp1_each_f64_host", ctx._h, X, Y, XI, lens, extrap, want_ok, ctx._h)
+
+
+def interp2_slices(ctx, ax, ay, Z, xi, yi, out=None, extrap=math.nan):
+    """mi_interp2_slices_f64_dev: arma::interp2's gridded output for every slice of a cube, Z read where it lies.
+    ax, ay: Axis1 (nx and ny nodes; the same object is allowed); Z: (ny, nx, S) float64 CUDA tensor laid out like an
+    arma::cube (see _cube_view; a padded view is taken as it is); xi, yi: contiguous float64 CUDA tensors in any order;
+    out: (nyi, nxi, S) tensor of the same layout (default: the .permute(2, 1, 0) view of a new contiguous (S, nxi, nyi)
+    buffer).  Returns out with out[i, j, s] = Z[:, :, s] at (xi[j], yi[i]), bit-identical to Grid2.interp_grid on that
+    slice; asynchronous on the context's stream."""
+    for t in (xi, yi):
+        _need_f64_cuda(t, "query axes", True, "query axes must be contiguous float64 CUDA tensors")
+    _need_f64_cuda(Z, "Z", False)
+    ldz, zstride, S = _cube_view(Z, ay.n, ax.n, "Z")
+    nxi, nyi = xi.numel(), yi.numel()
+    out = _out_cube(out, nyi, nxi, S, Z)
+    ldzi, zistride, So = _cube_view(out, nyi, nxi, "out")
+    if So != S:
+        raise ValueError("out must have as many slices as Z")
+    check(ctx._L.mi_interp2_slices_f64_dev(ctx._h, ax._h, ay._h, C.c_void_p(Z.data_ptr()), ldz, zstride, S, _ptr(xi), nxi,
+                                           _ptr(yi), nyi, C.c_void_p(out.data_ptr()), ldzi, zistride, float(extrap)), ctx._h)
+    return out
 
 
 # ---- the reference's own step: Restrict + masked mean (EventDrivenMap.cu:769-824) ----
@@ -559,210 +776,27 @@ def default_edm_params(**overrides):
     return p
 
 
+def _f_buffers(S, want_partial):
+    """(f, partial) host buffers of one evaluation; partial has MI_EDM_PARTIAL_LEN(S) = 2 S + 1 elements, or is None"""
+    return np.empty(S, dtype=np.float64), np.empty(2 * S + 1, dtype=np.float64) if want_partial else None
 
 
-def interp_pairs(ctx, X, Y, xi, lens=None, out=None, extrap=math.nan, want_ok=False):
-    """interp1 over paired columns (mi_interp1_pairs_f64_dev): column c of Y is sampled at the nodes in column c of X.
-
-    X, Y: (n, B) float64 CUDA tensors given as column-major views (Axis1's layout rules: the .T view of a contiguous
-    (B, ld) buffer; X and Y may have different leading dimensions); xi: contiguous float64 CUDA tensor of nxi queries in
-    any order, shared by every column; lens: optional contiguous (B,) int32 / uint32 CUDA tensor, the number of valid
-    leading rows of each column; out: column-major (nxi, B) tensor (default: the .T view of a new contiguous (B, nxi)
-    buffer).  X is validated on the device at every call: a column whose length is outside [2, n] or whose nodes are not
-    finite and strictly increasing gives NaN in all its outputs.  Returns the (nxi, B) result, or (result, ok) with
-    want_ok=True, ok a (B,) int32 CUDA tensor (1 good, 0 bad).  Asynchronous on the context's stream."""
-    torch = _torch()
-    if not (xi.is_cuda and xi.dtype == torch.float64 and xi.is_contiguous()):
-        raise ValueError("xi must be a contiguous float64 CUDA tensor")
-    if not (X.is_cuda and X.dtype == torch.float64 and Y.is_cuda and Y.dtype == torch.float64):
-        raise ValueError("X and Y must be float64 CUDA tensors")
-    if X.dim() != 2 or tuple(X.shape) != tuple(Y.shape):
-        raise ValueError("X and Y must both have shape (n, B)")
-    n = int(X.shape[0])
-    ldx, B = Axis1._colmajor_view(X, n, "X")
-    ldy, _ = Axis1._colmajor_view(Y, n, "Y")
-    nxi = xi.numel()
-    if lens is not None and not (lens.is_cuda and lens.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
-                                 and lens.is_contiguous() and tuple(lens.shape) == (B,)):
-        raise ValueError("lens must be a contiguous int32 CUDA tensor of shape (B,)")
-    if out is None:
-        out = torch.empty((B, nxi), dtype=torch.float64, device=Y.device).T
-    elif not (out.is_cuda and out.dtype == torch.float64):
-        raise ValueError("out must be a float64 CUDA tensor")
-    ldyi, Bo = Axis1._colmajor_view(out, nxi, "out")
-    if Bo != B:
-        raise ValueError("out must have as many columns as Y")
-    ok = torch.empty((B,), dtype=torch.int32, device=Y.device) if want_ok else None
-    check(ctx._L.mi_interp1_pairs_f64_dev(ctx._h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, n,
-                                          C.c_void_p(lens.data_ptr()) if lens is not None else None, B, _ptr(xi), nxi,
-                                          C.c_void_p(out.data_ptr()), ldyi, float(extrap),
-                                          C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
-    return (out, ok) if want_ok else out
-
-
-def _pairs_host_args(X, Y, xi, lens):
-    xi = _np64(xi)
-    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
-    if X.ndim != 2 or X.shape != Y.shape:
-        raise ValueError("X and Y must both have shape (n, B)")
-    X = X if X.flags["F_CONTIGUOUS"] else np.asfortranarray(X)
-    Y = Y if Y.flags["F_CONTIGUOUS"] else np.asfortranarray(Y)
-    n, B = X.shape
-    if lens is not None:
-        lens = np.ascontiguousarray(np.asarray(lens).reshape(-1).astype(np.uint32, casting="unsafe"))
-        if lens.size != B:
-            raise ValueError("lens must hold one count per column")
-    return X, Y, xi, lens, n, B
-
-
-def interp_pairs_host(ctx, X, Y, xi, lens=None, extrap=math.nan, want_ok=False):
-    """host form of interp_pairs (mi_interp1_pairs_f64_host): (n, B) numpy arrays (any layout; column-major ones are
-    used in place), numpy queries and counts; returns a Fortran-ordered (nxi, B) array, or (array, ok) with want_ok=True
-    (ok: (B,) uint32).  Synchronous.  Without want_ok a bad column raises MiError (code 2, MI_ERR_GRID)."""
-    X, Y, xi, lens, n, B = _pairs_host_args(X, Y, xi, lens)
-    out = np.empty((B, xi.size)).T
-    ok = np.ones(B, dtype=np.uint32) if want_ok else None
-    check(ctx._L.mi_interp1_pairs_f64_host(ctx._h, C.c_void_p(X.ctypes.data), max(n, 1), C.c_void_p(Y.ctypes.data), max(n, 1), n,
-                                           _ptr(lens) if lens is not None else None, B, _ptr(xi), xi.size,
-                                           C.c_void_p(out.ctypes.data), max(xi.size, 1), float(extrap),
-                                           _ptr(ok) if want_ok else None), ctx._h)
-    return (out, ok) if want_ok else out
-
-def interp_each(ctx, X, Y, XI, lens=None, out=None, extrap=math.nan, want_ok=False):
-    """interp1 over paired columns with a query vector per column (mi_interp1_each_f64_dev): column c of Y, sampled at
-    the nodes in column c of X, is evaluated at the queries in column c of XI.
-
-    X, Y, lens, out, the validation of X and the return value are interp_pairs'.  XI is either a column-major (nxi, B)
-    float64 CUDA view (Axis1's layout rules; its own leading dimension): the queries of each column -- or a contiguous
-    1-D float64 CUDA tensor of nxi queries shared by every column (ldxi = 0): bit-identical to interp_pairs, and served by
-    the thin one-lane-per-column kernel when the columns are very short.  Asynchronous on the context's stream."""
-    torch = _torch()
-    if not (XI.is_cuda and XI.dtype == torch.float64):
-        raise ValueError("XI must be a float64 CUDA tensor")
-    if not (X.is_cuda and X.dtype == torch.float64 and Y.is_cuda and Y.dtype == torch.float64):
-        raise ValueError("X and Y must be float64 CUDA tensors")
-    if X.dim() != 2 or tuple(X.shape) != tuple(Y.shape):
-        raise ValueError("X and Y must both have shape (n, B)")
-    n = int(X.shape[0])
-    ldx, B = Axis1._colmajor_view(X, n, "X")
-    ldy, _ = Axis1._colmajor_view(Y, n, "Y")
-    if XI.dim() == 1:
-        if not XI.is_contiguous():
-            raise ValueError("a shared XI must be a contiguous 1-D tensor")
-        nxi, ldxi = XI.numel(), 0
-    else:
-        if XI.dim() != 2:
-            raise ValueError("XI must be a column-major (nxi, B) view or a contiguous 1-D tensor")
-        nxi = int(XI.shape[0])
-        ldxi, Bq = Axis1._colmajor_view(XI, nxi, "XI")
-        if Bq != B:
-            raise ValueError("XI must have as many columns as X")
-    if lens is not None and not (lens.is_cuda and lens.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
-                                 and lens.is_contiguous() and tuple(lens.shape) == (B,)):
-        raise ValueError("lens must be a contiguous int32 CUDA tensor of shape (B,)")
-    if out is None:
-        out = torch.empty((B, nxi), dtype=torch.float64, device=Y.device).T
-    elif not (out.is_cuda and out.dtype == torch.float64):
-        raise ValueError("out must be a float64 CUDA tensor")
-    ldyi, Bo = Axis1._colmajor_view(out, nxi, "out")
-    if Bo != B:
-        raise ValueError("out must have as many columns as Y")
-    ok = torch.empty((B,), dtype=torch.int32, device=Y.device) if want_ok else None
-    check(ctx._L.mi_interp1_each_f64_dev(ctx._h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, n,
-                                         C.c_void_p(lens.data_ptr()) if lens is not None else None, B,
-                                         C.c_void_p(XI.data_ptr()), ldxi, nxi, C.c_void_p(out.data_ptr()), ldyi, float(extrap),
-                                         C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
-    return (out, ok) if want_ok else out
-
-
-def _each_host_args(X, Y, XI, lens):
-    """the host forms' arguments: (X, Y, XI, lens, n, B, nxi, ldxi); a 2-D XI must be (nxi, B), a 1-D one is shared"""
-    XI = np.asarray(XI, dtype=np.float64)
-    if XI.ndim == 1:
-        X, Y, xi, lens, n, B = _pairs_host_args(X, Y, XI, lens)
-        return X, Y, xi, lens, n, B, xi.size, 0
-    X, Y, _, lens, n, B = _pairs_host_args(X, Y, np.zeros(0), lens)
-    if XI.ndim != 2 or XI.shape[1] != B:
-        raise ValueError("XI must have shape (nxi, B), one column of queries per column of X, or be 1-D")
-    XI = XI if XI.flags["F_CONTIGUOUS"] else np.asfortranarray(XI)
-    return X, Y, XI, lens, n, B, XI.shape[0], max(XI.shape[0], 1)
-
-
-def interp_each_host(ctx, X, Y, XI, lens=None, extrap=math.nan, want_ok=False):
-    """host form of interp_each (mi_interp1_each_f64_host): (n, B) numpy arrays, XI an (nxi, B) array (any layout;
-    column-major ones are used in place) or a 1-D array shared by every column; returns a Fortran-ordered (nxi, B) array,
-    or (array, ok) with want_ok=True.  Synchronous.  Without want_ok a bad column raises MiError (code 2, MI_ERR_GRID)."""
-    X, Y, XI, lens, n, B, nxi, ldxi = _each_host_args(X, Y, XI, lens)
-    out = np.empty((B, nxi)).T
-    ok = np.ones(B, dtype=np.uint32) if want_ok else None
-    check(ctx._L.mi_interp1_each_f64_host(ctx._h, C.c_void_p(X.ctypes.data), max(n, 1), C.c_void_p(Y.ctypes.data), max(n, 1), n,
-                                          _ptr(lens) if lens is not None else None, B, C.c_void_p(XI.ctypes.data), ldxi, nxi,
-                                          C.c_void_p(out.ctypes.data), max(nxi, 1), float(extrap),
-                                          _ptr(ok) if want_ok else None), ctx._h)
-    return (out, ok) if want_ok else out
-
-
-def _cube_view(a, rows, cols, what):
-    """(leading dimension, slice stride, slices) of a 3-D (rows, cols, S) array or tensor stored like an arma::cube:
-    element (i, j, s) at i + j*ld + s*stride, i.e. the .permute(2, 1, 0) view of a contiguous (S, cols, rows) buffer, or
-    a padded view of one; strides in elements"""
-    shape = tuple(a.shape)
-    if len(shape) != 3 or shape[0] != rows or shape[1] != cols:
-        raise ValueError("%s must have shape (%d, %d, S)" % (what, rows, cols))
-    st = a.stride() if hasattr(a, "stride") else tuple(s // a.itemsize for s in a.strides)
-    S = shape[2]
-    ld = st[1] if cols > 1 else max(rows, 1)
-    stride = st[2] if S > 1 else ld * cols
-    if (rows > 1 and st[0] != 1) or ld < rows or stride < ld * cols:
-        raise ValueError("%s must be stored slice by slice, column-major inside a slice (the .permute(2, 1, 0) view of a "
-                         "contiguous (S, %d, %d) buffer)" % (what, cols, rows))
-    return ld, stride, S
-
-
-def interp2_slices(ctx, ax, ay, Z, xi, yi, out=None, extrap=math.nan):
-    """mi_interp2_slices_f64_dev: arma::interp2's gridded output for every slice of a cube, Z read where it lies.
-    ax, ay: Axis1 (nx and ny nodes; the same object is allowed); Z: (ny, nx, S) float64 CUDA tensor laid out like an
-    arma::cube (see _cube_view; a padded view is taken as it is); xi, yi: contiguous float64 CUDA tensors in any order;
-    out: (nyi, nxi, S) tensor of the same layout (default: the .permute(2, 1, 0) view of a new contiguous (S, nxi, nyi)
-    buffer).  Returns out with out[i, j, s] = Z[:, :, s] at (xi[j], yi[i]), bit-identical to Grid2.interp_grid on that
-    slice; asynchronous on the context's stream."""
-    torch = _torch()
-    for t in (xi, yi):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise ValueError("query axes must be contiguous float64 CUDA tensors")
-    if not (Z.is_cuda and Z.dtype == torch.float64):
-        raise ValueError("Z must be a float64 CUDA tensor")
-    ldz, zstride, S = _cube_view(Z, ay.n, ax.n, "Z")
-    nxi, nyi = xi.numel(), yi.numel()
-    if out is None:
-        out = torch.empty((S, nxi, nyi), dtype=torch.float64, device=Z.device).permute(2, 1, 0)
-    elif not (out.is_cuda and out.dtype == torch.float64):
-        raise ValueError("out must be a float64 CUDA tensor")
-    ldzi, zistride, So = _cube_view(out, nyi, nxi, "out")
-    if So != S:
-        raise ValueError("out must have as many slices as Z")
-    check(ctx._L.mi_interp2_slices_f64_dev(ctx._h, ax._h, ay._h, C.c_void_p(Z.data_ptr()), ldz, zstride, S, _ptr(xi), nxi,
-                                           _ptr(yi), nyi, C.c_void_p(out.data_ptr()), ldzi, zistride, float(extrap)), ctx._h)
-    return out
-
-
-class EventDrivenMap:
+class EventDrivenMap(_Handle):
     """Mirror of the reference class: ComputeF(Z) -> f through lift/evolve/restrict/average."""
+    _destroy = "mi_edm_destroy"
 
     def __init__(self, ctx, parameters, noReal, **overrides):
-        self._ctx, self._L = ctx, ctx._L
+        self._ctx = ctx
         par = np.atleast_1d(np.asarray(parameters, dtype=np.float64))
         self.params = default_edm_params(beta_mean=float(np.float32(par[0])), n_real=int(noReal), **overrides)
         h = C.c_void_p()
-        check(self._L.mi_edm_create(ctx._h, C.byref(self.params), C.byref(h)), ctx._h)
-        self._h = h
+        check(ctx._L.mi_edm_create(ctx._h, C.byref(self.params), C.byref(h)), ctx._h)
+        self._own(ctx._L, h, ctx)
         # test / tuning hooks of the Python layer (the library itself reads no environment for this): force an evolve
         # kernel form, switch the exact quotient by launch-uniform divisors off.  Results are bit-identical either way.
         wpr = os.environ.get("MI_EDM_WAVES_PER_REALISATION", "")
         if wpr in ("1", "4") or "MI_EDM_NO_UNIFORM_DIV" in os.environ:
             self.set_kernel_choice(int(wpr) if wpr in ("1", "4") else 0, "MI_EDM_NO_UNIFORM_DIV" not in os.environ)
-        if hasattr(ctx, "_children"):
-            ctx._children.add(self)
 
     def _push(self):
         check(self._L.mi_edm_set_params(self._h, C.byref(self.params)), self._ctx._h)
@@ -811,8 +845,7 @@ class EventDrivenMap:
         S = int(self.params.n_spikes)
         if Z.size != S:
             raise ValueError("Z must have n_spikes=%d elements" % S)
-        f = np.empty(S, dtype=np.float64)
-        partial = np.empty(2 * S + 1, dtype=np.float64) if want_partial else None   # MI_EDM_PARTIAL_LEN(S)
+        f, partial = _f_buffers(S, want_partial)
         check(self._L.mi_edm_compute_f(self._h, _ptr(Z), _ptr(f), _ptr(partial) if want_partial else None),
               self._ctx._h)
         return (f, partial) if want_partial else f
@@ -825,9 +858,7 @@ class EventDrivenMap:
         check(self._L.mi_edm_compute_f_begin(self._h, _ptr(Z)), self._ctx._h)
 
     def end(self, want_partial=False):
-        S = int(self.params.n_spikes)
-        f = np.empty(S, dtype=np.float64)
-        partial = np.empty(2 * S + 1, dtype=np.float64) if want_partial else None   # MI_EDM_PARTIAL_LEN(S)
+        f, partial = _f_buffers(int(self.params.n_spikes), want_partial)
         check(self._L.mi_edm_compute_f_end(self._h, _ptr(f), _ptr(partial) if want_partial else None), self._ctx._h)
         return (f, partial) if want_partial else f
 
@@ -899,15 +930,7 @@ class EventDrivenMap:
         for rep in getattr(self, "_replicas", None) or []:
             rep.close()
         self._replicas = []
-        if getattr(self, "_h", None):
-            self._L.mi_edm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 def _edm_debug_read(L, h, params, ctx_h=None):
@@ -948,17 +971,19 @@ class _GroupCtx:
         return Context.device_info(self)
 
 
-class Group:
+class Group(_Handle):
     """One process driving several GPUs: devices = [0, 1, ..] (a repeated ordinal rehearses the sharding on one GPU)."""
     REDUCE_HOST, REDUCE_RCCL = 0, 1
+    _destroy = "mi_group_destroy"
 
     def __init__(self, devices):
-        self._L = _lib.load()
+        L = _lib.load()
         devices = list(range(devices)) if isinstance(devices, int) else [int(d) for d in devices]
         arr = (C.c_int * len(devices))(*devices)
         h = C.c_void_p()
-        check(self._L.mi_group_create(len(devices), arr, C.byref(h)))
-        self._h, self.devices = h, devices
+        check(L.mi_group_create(len(devices), arr, C.byref(h)))
+        self._own(L, h)
+        self.devices = devices
 
     def __len__(self):
         return int(self._L.mi_group_size(self._h))
@@ -1009,60 +1034,29 @@ class Group:
     def interp_cols_host(self, X, Y, xi, extrap=math.nan):
         """interp1 over the columns of Y (Axis1.interp_cols_host) with the columns sharded over the group's devices;
         X (n nodes, used as given) and xi are replicated.  Y: (n, B) numpy array; returns a Fortran-ordered (nxi, B) array."""
-        X, xi = _np64(X), _np64(xi)
-        Y = np.asarray(Y, dtype=np.float64)
-        if Y.ndim != 2 or Y.shape[0] != X.size:
-            raise ValueError("Y must have shape (len(X), B)")
-        if not Y.flags["F_CONTIGUOUS"]:
-            Y = np.asfortranarray(Y)
-        B = Y.shape[1]
-        out = np.empty((B, xi.size)).T
-        check(self._L.mi_group_interp1_cols_f64_host(self._h, _ptr(X), X.size, C.c_void_p(Y.ctypes.data), X.size, B, _ptr(xi),
-                                                     xi.size, C.c_void_p(out.ctypes.data), xi.size, float(extrap)))
-        return out
+        X = _np64(X)
+        return _cols_host(self._L, "mi_group_interp1_cols_f64_host", (self._h, _ptr(X), X.size), X.size, "len(X)", Y, xi, extrap)
 
     def interp_pairs_host(self, X, Y, xi, lens=None, extrap=math.nan, want_ok=False):
         """interp1 over paired columns (interp_pairs_host) with the columns sharded over the group's devices; xi is
         replicated.  Returns a Fortran-ordered (nxi, B) array, or (array, ok) with want_ok=True."""
-        X, Y, xi, lens, n, B = _pairs_host_args(X, Y, xi, lens)
-        out = np.empty((B, xi.size)).T
-        ok = np.ones(B, dtype=np.uint32) if want_ok else None
-        check(self._L.mi_group_interp1_pairs_f64_host(self._h, C.c_void_p(X.ctypes.data), max(n, 1), C.c_void_p(Y.ctypes.data),
-                                                      max(n, 1), n, _ptr(lens) if lens is not None else None, B, _ptr(xi),
-                                                      xi.size, C.c_void_p(out.ctypes.data), max(xi.size, 1), float(extrap),
-                                                      _ptr(ok) if want_ok else None))
-        return (out, ok) if want_ok else out
+        return _pairs_host(self._L, "mi_group_interp1_pairs_f64_host", self._h, X, Y, xi, lens, extrap, want_ok)
 
     def interp_each_host(self, X, Y, XI, lens=None, extrap=math.nan, want_ok=False):
         """interp1 over paired columns with a query vector per column (interp_each_host) with the columns sharded over
         the group's devices; a 2-D XI is sharded with its columns, a 1-D one is replicated."""
-        X, Y, XI, lens, n, B, nxi, ldxi = _each_host_args(X, Y, XI, lens)
-        out = np.empty((B, nxi)).T
-        ok = np.ones(B, dtype=np.uint32) if want_ok else None
-        check(self._L.mi_group_interp1_each_f64_host(self._h, C.c_void_p(X.ctypes.data), max(n, 1), C.c_void_p(Y.ctypes.data),
-                                                     max(n, 1), n, _ptr(lens) if lens is not None else None, B,
-                                                     C.c_void_p(XI.ctypes.data), ldxi, nxi, C.c_void_p(out.ctypes.data),
-                                                     max(nxi, 1), float(extrap), _ptr(ok) if want_ok else None))
-        return (out, ok) if want_ok else out
+        return _each_host(self._L, "mi_group_interp1_each_f64_host", self._h, X, Y, XI, lens, extrap, want_ok)
 
     def edm(self, parameters, noReal, **overrides):
         return GroupEventDrivenMap(self, parameters, noReal, **overrides)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mi_group_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class GroupGrid1(_Handle):
+    _destroy = "mi_group_grid1_destroy"
 
-
-class GroupGrid1:
     def __init__(self, group, h):
-        self._g, self._L, self._h = group, group._L, h
+        self._g = group
+        self._own(group._L, h)
 
     def interp_host(self, xq, extrap=math.nan):
         """host arrays in, host array out; the queries are sharded over the group's devices"""
@@ -1097,21 +1091,13 @@ class GroupGrid1:
             self._g.synchronize()
         return (outs, full) if gather else outs
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mi_group_grid1_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class GroupGrid2(_Handle):
+    _destroy = "mi_group_grid2_destroy"
 
-
-class GroupGrid2:
     def __init__(self, group, h):
-        self._g, self._L, self._h = group, group._L, h
+        self._g = group
+        self._own(group._L, h)
 
     def interp_host(self, xq, yq, extrap=math.nan):
         """host arrays in, host array out; the scattered queries are sharded over the group's devices"""
@@ -1147,37 +1133,25 @@ class GroupGrid2:
         self._g.synchronize()
         return (outs, full) if gather else outs
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mi_group_grid2_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class GroupEventDrivenMap:
+class GroupEventDrivenMap(_Handle):
     """EventDrivenMap with the realisations sharded over a Group; noReal is the total."""
+    _destroy = "mi_group_edm_destroy"
 
     def __init__(self, group, parameters, noReal, **overrides):
-        self._g, self._L = group, group._L
+        self._g = group
         par = np.atleast_1d(np.asarray(parameters, dtype=np.float64))
         self.params = default_edm_params(beta_mean=float(np.float32(par[0])), n_real=int(noReal), **overrides)
         h = C.c_void_p()
-        check(self._L.mi_group_edm_create(group._h, C.byref(self.params), C.byref(h)))
-        self._h = h
+        check(group._L.mi_group_edm_create(group._h, C.byref(self.params), C.byref(h)))
+        self._own(group._L, h)
 
     def _push(self):
         check(self._L.mi_group_edm_set_params(self._h, C.byref(self.params)))
 
     def ComputeF(self, Z, want_partial=False):
         Z = _np64(Z)
-        S = int(self.params.n_spikes)
-        f = np.empty(S, dtype=np.float64)
-        partial = np.empty(2 * S + 1, dtype=np.float64)
+        f, partial = _f_buffers(int(self.params.n_spikes), True)       # partial is always asked for, returned only if wanted
         check(self._L.mi_group_edm_compute_f(self._h, _ptr(Z), _ptr(f), _ptr(partial)))
         return (f, partial) if want_partial else f
 
@@ -1197,14 +1171,3 @@ class GroupEventDrivenMap:
         C.memmove(C.byref(par), C.byref(self.params), C.sizeof(EdmParams))
         par.n_real = hi - lo
         return _edm_debug_read(self._L, C.c_void_p(h), par)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.mi_group_edm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
