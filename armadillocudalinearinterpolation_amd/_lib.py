@@ -52,6 +52,7 @@ SIGNATURES = {
     "mi_debug_each_launches": (_sz, [_i32]),
     "mi_debug_slices2_launches": (_sz, [_i32]),
     "mi_debug_rows1_launches": (_sz, [_i32]),
+    "mi_debug_rowpairs_launches": (_sz, [_i32]),
     "mi_debug_grid1_formula": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "mi_last_error": (C.c_char_p, [_vp]),
     "mi_ctx_create": (_i32, [_i32, _pp]),
@@ -93,6 +94,7 @@ SIGNATURES = {
     "mi_interp1_each_f64_host": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp2_slices_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl]),
     "mi_interp1_rows_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
+    "mi_interp1_rowpairs_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _dbl, _vp]),
     "mi_restrict_f32_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _vp, _sz]),
     "mi_restrict_f32_host": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _vp, _sz]),
     "mi_masked_mean_f32_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _i32, _vp, _vp, _vp]),

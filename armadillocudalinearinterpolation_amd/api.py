@@ -568,6 +568,14 @@ def _cols_host(L, fn, table, n, n_words, Y, xi, extrap, ctx_h=None):
 
 # ---- interp1 over paired columns, and interp2 over the slices of a cube -------------------------------------------
 
+def _need_lens(lens, count, letter):
+    """ValueError unless lens is None or a contiguous (count,) int32 / uint32 CUDA tensor; letter names count in the message"""
+    torch = _torch()
+    if lens is not None and not (lens.is_cuda and lens.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                 and lens.is_contiguous() and tuple(lens.shape) == (count,)):
+        raise ValueError("lens must be a contiguous int32 CUDA tensor of shape (%s,)" % letter)
+
+
 def _paired_args(X, Y, queries, lens, out, want_ok):
     """What interp_pairs and interp_each share, checked in the order both keep: X and Y, then the queries -- the one
     step that differs: queries(B) returns (nxi, ldxi) -- then lens, out and ok.
@@ -581,9 +589,7 @@ def _paired_args(X, Y, queries, lens, out, want_ok):
     ldx, B = Axis1._colmajor_view(X, n, "X")
     ldy, _ = Axis1._colmajor_view(Y, n, "Y")
     nxi, ldxi = queries(B)
-    if lens is not None and not (lens.is_cuda and lens.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
-                                 and lens.is_contiguous() and tuple(lens.shape) == (B,)):
-        raise ValueError("lens must be a contiguous int32 CUDA tensor of shape (B,)")
+    _need_lens(lens, B, "B")
     out, ldyi = _out_colmajor(out, nxi, B, Y)
     ok = torch.empty((B,), dtype=torch.int32, device=Y.device) if want_ok else None
     return n, B, ldx, ldy, nxi, ldxi, out, ldyi, ok
@@ -605,6 +611,37 @@ def interp_pairs(ctx, X, Y, xi, lens=None, out=None, extrap=math.nan, want_ok=Fa
                                           C.c_void_p(lens.data_ptr()) if lens is not None else None, B, _ptr(xi), nxi,
                                           C.c_void_p(out.data_ptr()), ldyi, float(extrap),
                                           C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
+    return (out, ok) if want_ok else out
+
+
+def interp_rowpairs(ctx, X, Y, xi, lens=None, out=None, extrap=math.nan, want_ok=False):
+    """interp1 over paired rows (mi_interp1_rowpairs_f64_dev): row r of Y is sampled at the nodes in row r of X --
+    interp_pairs for data stored the other way round, realisation-fastest, without a transpose.
+
+    X, Y: (m, n) float64 CUDA tensors in the rows layout (Axis1._rows_view's rule: the .T view of a contiguous (n, ld)
+    buffer, or a padded view of one; X and Y may have different leading dimensions); xi: contiguous float64 CUDA tensor of
+    nxi queries in any order, shared by every row; lens: optional contiguous (m,) int32 / uint32 CUDA tensor, the number
+    of valid leading nodes of each row; out: (m, nxi) tensor in the same layout (default: the .T view of a new contiguous
+    (nxi, m) buffer).  X is validated on the device at every call: a row whose length is outside [2, n] or whose nodes are
+    not finite and strictly increasing gives NaN in all its outputs.  Returns the (m, nxi) result, or (result, ok) with
+    want_ok=True, ok an (m,) int32 CUDA tensor (1 good, 0 bad).  Asynchronous on the context's stream."""
+    torch = _torch()
+    _need_f64_cuda(xi, "xi", True)
+    for t in (X, Y):
+        _need_f64_cuda(t, "X and Y", False, "X and Y must be float64 CUDA tensors")
+    if X.dim() != 2 or tuple(X.shape) != tuple(Y.shape):
+        raise ValueError("X and Y must both have shape (m, n)")
+    n = int(X.shape[1])
+    ldx, m = Axis1._rows_view(X, n, "X")
+    ldy, _ = Axis1._rows_view(Y, n, "Y")
+    _need_lens(lens, m, "m")
+    nxi = xi.numel()
+    out, ldyi = _out_rows(out, m, nxi, Y)
+    ok = torch.empty((m,), dtype=torch.int32, device=Y.device) if want_ok else None
+    check(ctx._L.mi_interp1_rowpairs_f64_dev(ctx._h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, m, n,
+                                             C.c_void_p(lens.data_ptr()) if lens is not None else None, _ptr(xi), nxi,
+                                             C.c_void_p(out.data_ptr()), ldyi, float(extrap),
+                                             C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
     return (out, ok) if want_ok else out
 
 

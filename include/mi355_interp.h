@@ -60,6 +60,8 @@ extern "C" {
  *                short columns); mi_interp2_slices_f64_dev, mi_debug_slices2_launches (gridded interp2 over the slices of a
  *                cube, Z read in place; device form); mi_interp1_rows_f64_dev, mi_debug_rows1_launches (interp1 along
  *                the rows of a matrix / across the slices of a cube: one X, a table per row; device form only);
+ *                mi_interp1_rowpairs_f64_dev, mi_debug_rowpairs_launches (interp1 over paired rows: every row of Y with
+ *                its own X, realisation-fastest data; device form only);
  *                mi_group_wait_stream (a group member's stream behind a stream of the caller's) */
 #define MI355_INTERP_ABI_VERSION 4
 
@@ -108,6 +110,9 @@ size_t mi_debug_slices2_launches(int form);
 /* Test hook: calls of mi_interp1_rows_f64_dev by this process so far that took the given form: 0 tile body with 16-B
  * accesses, 1 tile body with 8-B accesses, 2 flat body (m < 256); 0 for any other value of form. */
 size_t mi_debug_rows1_launches(int form);
+/* Test hook: calls of mi_interp1_rowpairs_f64_dev by this process so far that took the given form: 0 short-row form
+ * (n <= 32, one launch), 1 long-row form (validation pass, then the march); 0 for any other value of form. */
+size_t mi_debug_rowpairs_launches(int form);
 /* Test hook: which closed form of the abscissae a mode-0 table evaluates (0 fma(i, dx, x0); 1 x0 + i*dx;
  * 2 x0 + span*(i/(n-1)); 3 the same with the quotient from a Markstein step) and whether its last node is pinned to
  * xmax -- i.e. which instance of the interp1 kernels a call on this table launches.  Both are -1 for the {x,y} modes. */
@@ -278,7 +283,8 @@ mi_status mi_interp1_cols_f64_host(mi_ctx* ctx, const mi_axis1* axis, const doub
  * way; the status is MI_ERR_GRID (the text names the first bad column) when at least one column is bad and col_ok is
  * NULL, MI_OK when col_ok was given.
  * Which call when: one X for every column -> mi_interp1_cols_f64_dev (it locates each query once per call); an X per
- * column -> this call; one column with many queries -> mi_grid1 and mi_interp1_f64_dev. */
+ * column -> this call; one column with many queries -> mi_grid1 and mi_interp1_f64_dev; the same data stored the other
+ * way round, an X per ROW -> mi_interp1_rowpairs_f64_dev, without a transpose. */
 mi_status mi_interp1_pairs_f64_dev(mi_ctx* ctx, const double* x_dev, size_t ldx, const double* y_dev, size_t ldy, size_t n,
                                    const uint32_t* len_dev, size_t ncols, const double* xi_dev, size_t nxi,
                                    double* yi_dev, size_t ldyi, double extrap_val, uint32_t* col_ok_dev);
@@ -370,9 +376,57 @@ mi_status mi_interp2_slices_f64_dev(mi_ctx* ctx, const mi_axis1* ax, const mi_ax
  * sizes whose byte counts overflow (ldy*n, ldyi*nxi, nxi*16).
  * There is no host-pointer, group or arma:: form of this call.
  * Which call when: one table per ROW, or interpolation across the slices of a cube -> this call; one table per column ->
- * mi_interp1_cols_f64_dev; a single row with many queries (m == 1) -> mi_grid1 and mi_interp1_f64_dev. */
+ * mi_interp1_cols_f64_dev; a single row with many queries (m == 1) -> mi_grid1 and mi_interp1_f64_dev; one table per row
+ * AND an X per row -> mi_interp1_rowpairs_f64_dev. */
 mi_status mi_interp1_rows_f64_dev(mi_ctx* ctx, const mi_axis1* axis, const double* y_dev, size_t ldy, size_t m,
                                   const double* xi_dev, size_t nxi, double* yi_dev, size_t ldyi, double extrap_val);
+
+/* ---- interp1 over paired rows (an X per row of Y) ---------------------------
+ * mi_interp1_pairs_f64_dev for data stored the other way round: row r of y is sampled at the nodes in row r of x.  An
+ * ensemble stored realisation-fastest, one time level per contiguous block (the reference's [spike][realisation] event
+ * arrays, index m*R + r), every trajectory recorded at its own event times, resampled onto one common mesh where it
+ * lies; with n = 2 and nxi = 1 it is the shape of the reference's RestrictKernel in fp64.  The contract is
+ * mi_interp1_pairs_f64_dev's word for word, with rows in place of columns:
+ *     x:  column-major m x n,    X(r, k) = x[r + k*ldx],  ldx >= m,
+ *     y:  column-major m x n,    Y(r, k) = y[r + k*ldy],  ldy >= m,
+ *     yi: column-major m x nxi,  yi[r + i*ldyi],          ldyi >= m,
+ * len (optional, NULL: n everywhere) holds one uint32 per row, the number n_r of valid leading nodes of that row,
+ * 2 <= n_r <= n; xi holds nxi queries in any order, shared by every row:
+ *     yi[r + i*ldyi] == what mi_interp1_f64_dev returns for xi[i] on the table (X(r, 0:n_r), Y(r, 0:n_r)) built without
+ *                       MI_GRID_SANITISE,  bit for bit
+ * (the fp64 blend at the top of this header, (1-w)*Y(r,l) + w*Y(r,rr) with rr = min(l+1, n_r-1), every operation rounded,
+ * no FMA; extrap_val outside [X(r,0), X(r,n_r-1)], NaN for a NaN query; inf / NaN / -0.0 inside a row of y go through the
+ * two-term blend and never reach another row).  Nodes k >= n_r of a row, rows m..ld-1 of any operand and padding never
+ * influence anything; rows m..ldyi-1 of yi are never written; yi must not overlap an input.
+ *
+ * x is validated on the device, at every call, with mi_axis1_create's rule.  A row is BAD when n_r < 2, n_r > n, any of
+ * X(r, 0:n_r) is not finite, or X(r, 0:n_r) is not strictly increasing (!(X(r,k-1) < X(r,k)): equal nodes and the pair
+ * -0.0, 0.0 are bad; x is never sorted for the caller).  All nxi outputs of a bad row are NaN whatever the queries and
+ * extrap_val; no other row is affected.  row_ok (optional) receives one uint32 per row: 1 good, 0 bad.  Bad rows are
+ * data, found asynchronously: the status is MI_OK.
+ *
+ * Device form only: device pointers; doubles 8-B aligned, len / row_ok 4-B aligned; 2 <= n < 2^31 - 16; asynchronous on
+ * the context's stream, no copy, no synchronisation; m == 0 or nxi == 0 is MI_OK with nothing launched or written.
+ * MI_ERR_INVALID_ARG for NULL or misaligned pointers, ldx < m, ldy < m, ldyi < m, n < 2, sizes whose byte counts overflow
+ * (ldx*n, ldy*n, ldyi*nxi, m*4).  A lane owns a row and marches along it as the (shared) queries go by; sorted xi makes
+ * that one pass over x and y, any other order stays correct and costs a binary search of the row per jump
+ * (csrc/mi_rowpairs1.hip; mi_debug_rowpairs_launches tells the form).  Allocation: none for n <= 32 (rows are validated
+ * inside the one kernel).  For longer rows a validation pass writes one flag per row first: into row_ok_dev when the
+ * caller gave one, otherwise into the context's record workspace (4 B per row, grown on demand, shared in stream order
+ * with mi_interp2_grid_f64_dev, mi_interp1_cols_f64_dev, mi_interp1_rows_f64_dev, mi_interp2_slices_f64_dev and the
+ * long-column forms of the paired-column calls) -- so with row_ok_dev the call never allocates, and it can be captured
+ * into a hipGraph once any workspace has grown.
+ * Out of scope: there is no host-pointer, group or arma:: form of this call (they wait for the cause of the open fault on
+ * the strided host-copy path; this call adds no host upload path), no query vector per row,
+ * and no fp32 form.
+ * Which call when: an X per ROW (realisation-fastest data), many rows, xi sorted or nearly so -> this call (measured
+ * 1.3-2.8x the transposing route); an X per column -> mi_interp1_pairs_f64_dev; one X for all rows ->
+ * mi_interp1_rows_f64_dev.  Two shapes are better served by a transpose and mi_interp1_pairs_f64_dev: xi in no order with
+ * long rows (this call then searches its row per output; measured 4x slower than that route at n = 1024), and a handful
+ * of very long rows (a lane per row leaves the machine empty; m = 8: 19x slower). */
+mi_status mi_interp1_rowpairs_f64_dev(mi_ctx* ctx, const double* x_dev, size_t ldx, const double* y_dev, size_t ldy,
+                                      size_t m, size_t n, const uint32_t* len_dev, const double* xi_dev, size_t nxi,
+                                      double* yi_dev, size_t ldyi, double extrap_val, uint32_t* row_ok_dev);
 
 /* ---- the reference's own interpolation ----------------------------------
  * Replaces RestrictKernel (EventDrivenMap.cu:769-785, launch :205-206):
