@@ -24,8 +24,8 @@
 //   direct form (n > kLdsMaxN, ldxi > 0): the validation pass (flags into col_ok or context scratch slot 3), then the
 //               column kernel on the column itself, reading its queries from xi + c*ldxi.
 // ldxi == 0 and not thin is mi_interp1_pairs_f64_dev's own case and is forwarded to it.
-// The staging helpers (ColLoad, col_issue, col_commit, search, skew, copy_cols) are copies of mi_pairs1.hip's: that file
-// is left as it is, so its five kernels keep their instruction streams by construction.
+// The LDS layout and the staging helpers (ColLoad, col_issue, col_commit, col_len, search, skew) are mi_paired_cols.hpp's,
+// shared with mi_pairs1.hip; the blend, the validation pass and the host side are still copies of that file's.
 // Every index into x, y, xi and yi is 64-bit; no grid dimension depends on B, n or nxi.
 #include <algorithm>
 #include <atomic>
@@ -35,10 +35,12 @@
 #include <vector>
 
 #include "mi_interp2_eval.hpp"
+#include "mi_paired_cols.hpp"
 
 namespace mi_each1 {
 
 using mi_interp2::kBlock;
+using namespace mi_paired;
 
 // The thin form's limits.  kThinMaxQ is the number of per-query register sets of the widest thin kernel (123 VGPRs, four
 // waves per SIMD).  Measured (scripts/gpu_interp1_each_timing.py): at n = 32, nxi = 8 the thin form is
@@ -46,133 +48,11 @@ using mi_interp2::kBlock;
 constexpr size_t kThinMaxN = 32;
 constexpr size_t kThinMaxQ = 8;
 
-constexpr int kQIter = 4;                            // as mi_pairs1.hip: 8 queries per lane in registers
 constexpr size_t kRowBlock = 2 * kBlock * kQIter;    // 2048 outputs of one column per unit
 constexpr size_t kLdsMaxN = 4096;                    // LDS form up to here (mi_pairs1.hip's limit and LDS budget: 133248 B)
-constexpr int kPrefetch = 2;
-constexpr int kWaves = kBlock / 64;
-constexpr size_t kFlagBytes = 4 * kWaves * sizeof(int);   // per wave: a validation flag for each buffer pair, padding
-
-typedef __attribute__((address_space(3))) double lds_double;
-typedef __attribute__((address_space(3))) int lds_int;
 
 // process-wide launch counts by form (mi_debug_each_launches): 0 thin, 1 LDS, 2 direct, 3 forwarded
 std::atomic<size_t> g_launches[4];
-
-__host__ __device__ inline int skew(int i) { return i + (i >> 5); }
-__host__ __device__ inline size_t x_stride(size_t n) { return n + (n >> 5) + 2; }
-__host__ __device__ inline size_t lds_bytes_for(size_t n) { return 2 * (x_stride(n) + n + 2) * sizeof(double) + kFlagBytes; }
-
-struct LdsX {                                        // the staged X of one column, skewed
-    lds_double* p;
-    __device__ __forceinline__ double operator[](int i) const { return p[skew(i)]; }
-};
-
-// ---- staging of one column into LDS: mi_pairs1.hip's helpers ------------------------------------------------------
-struct ColLoad {
-    d2 v[kPrefetch];
-    double seam[kPrefetch];
-    double first, last, before;
-    int h;
-    int nv;
-};
-
-template <bool CHECK>
-__device__ __forceinline__ void col_issue(ColLoad& L, const double* __restrict__ col, int n)
-{
-    L.h = (int)((reinterpret_cast<uintptr_t>(col) >> 3) & 1u);
-    L.nv = n > 0 ? (n - L.h) >> 1 : 0;
-    const d2* p = reinterpret_cast<const d2*>(col + L.h);
-    const bool lane0 = (threadIdx.x & 63u) == 0;
-#pragma unroll
-    for (int k = 0; k < kPrefetch; ++k) {
-        const int j = (int)threadIdx.x + k * kBlock;
-        L.v[k].x = 0.0;
-        L.v[k].y = 0.0;
-        L.seam[k] = -__builtin_inf();
-        if (j < L.nv) {
-            L.v[k] = __builtin_nontemporal_load(p + j);
-            if (CHECK && lane0 && L.h + 2 * j > 0) L.seam[k] = col[L.h + 2 * j - 1];
-        }
-    }
-    L.first = L.last = L.before = 0.0;
-    if (n > 0) {
-        L.first = col[0];
-        L.last = col[n - 1];
-        if (CHECK) L.before = col[n - 2];
-    }
-}
-
-__device__ __forceinline__ bool vec_bad(double prev, d2 v)
-{
-    return !(prev < v.x) | !(v.x < v.y) | !(v.y < __builtin_inf());
-}
-
-template <bool CHECK, bool SKEW>
-__device__ __forceinline__ bool col_commit(const ColLoad& L, const double* __restrict__ col, int n, lds_double* buf)
-{
-    bool bad = false;
-    auto at = [](int i) { return SKEW ? skew(i) : i; };
-    const bool lane0 = (threadIdx.x & 63u) == 0;
-#pragma unroll
-    for (int k = 0; k < kPrefetch; ++k) {
-        const int j = (int)threadIdx.x + k * kBlock;
-        double prev = 0.0;
-        if (CHECK) prev = __shfl_up(L.v[k].y, 1);
-        if (j < L.nv) {
-            buf[at(L.h + 2 * j)] = L.v[k].x;
-            buf[at(L.h + 2 * j + 1)] = L.v[k].y;
-            if (CHECK) bad |= vec_bad(lane0 ? L.seam[k] : prev, L.v[k]);
-        }
-    }
-    const d2* p = reinterpret_cast<const d2*>(col + L.h);
-    for (int j0 = kPrefetch * kBlock; j0 < L.nv; j0 += kBlock) {
-        const int j = j0 + (int)threadIdx.x;
-        d2 v;
-        v.x = 0.0;
-        v.y = 0.0;
-        if (j < L.nv) v = __builtin_nontemporal_load(p + j);
-        double prev = 0.0;
-        if (CHECK) prev = __shfl_up(v.y, 1);
-        if (j < L.nv) {
-            buf[at(L.h + 2 * j)] = v.x;
-            buf[at(L.h + 2 * j + 1)] = v.y;
-            if (CHECK) bad |= vec_bad(lane0 ? col[L.h + 2 * j - 1] : prev, v);
-        }
-    }
-    if (threadIdx.x == 0 && n > 0) {
-        buf[0] = L.first;
-        buf[at(n - 1)] = L.last;
-        buf[at(n)] = L.last;
-        if (CHECK) bad |= !(-__builtin_inf() < L.first) | !(L.before < L.last) | !(L.last < __builtin_inf());
-    }
-    return bad;
-}
-
-__device__ __forceinline__ int col_len(const uint32_t* __restrict__ len, size_t c, int n)
-{
-    if (!len) return n;
-    const uint32_t m = len[c];
-    return (m >= 2u && m <= (uint32_t)n) ? (int)m : 0;     // 0: out of range, the column is bad
-}
-
-template <typename XP>
-__device__ __forceinline__ void search(XP X, int nc, const double (&qa)[kQIter], const double (&qb)[kQIter], int (&la)[kQIter],
-                                       int (&lb)[kQIter])
-{
-#pragma unroll
-    for (int j = 0; j < kQIter; ++j) la[j] = lb[j] = 0;
-    for (int span = nc; span > 1;) {
-        const int half = span >> 1;
-#pragma unroll
-        for (int j = 0; j < kQIter; ++j) {
-            const double xa = X[la[j] + half], xb = X[lb[j] + half];
-            la[j] = (xa <= qa[j]) ? la[j] + half : la[j];
-            lb[j] = (xb <= qb[j]) ? lb[j] + half : lb[j];
-        }
-        span -= half;
-    }
-}
 
 // the blend and the range rule of interp1 on one located bracket
 __device__ __forceinline__ double finish(double xl, double xr, double yl, double yr, double q, double x0, double x1, double extrap)
@@ -361,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void each1_kernel(const double* __restrict_
             double* const out = yi + c * ldyi;
             int la[kQIter], lb[kQIter];
             double x0 = 0.0, x1 = 0.0;
-            const LdsX curx = {lds + (size_t)cb * pair};
+            const LdsX<true> curx = {lds + (size_t)cb * pair};
             lds_double* const cury = curx.p + sx;
             if (ok) {                                        // (uniform; a bad column is not searched: nc may be 0)
                 if constexpr (LDSF) {
