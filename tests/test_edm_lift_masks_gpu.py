@@ -7,7 +7,8 @@ At the reference's parameters slot == slice and the partial slice is dead, alway
 (shown to be what they claim by tests/test_edm_lift_masks_cpu.py) evolve full masks, masks with a dead head, live partial
 slices, four and five bumps and per-neuron beta for hundreds to thousands of events, in every evolve form: the
 throughput form with and without the exact quotient by uniform divisors, the latency form (which carries every slice
-and must agree), and the automatic choice.  EXACT math only: FAST math has no stated tolerance at these inputs.
+and must agree), and the automatic choice.  EXACT math here; under FAST math the same cases are held to the latency
+form bit for bit, form against form and against the tapped kernel, by tests/test_edm_fast_gpu.py.
 
 One session context, no group and no host-array entry point."""
 import functools
