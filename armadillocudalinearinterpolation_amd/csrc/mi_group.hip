@@ -14,8 +14,11 @@
 // copies and reduces on the host.
 #include <dlfcn.h>
 
+#include <cstdlib>
+#include <initializer_list>
 #include <new>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 #include "mi_common.hpp"
@@ -127,6 +130,93 @@ mi_status member_event(mi_group* g, std::vector<hipEvent_t>& v, size_t r, hipEve
             return mi::fail(nullptr, MI_ERR_HIP, "%s failed: %s", #call,                              \
                             (g)->GetErrorString ? (g)->GetErrorString(r_) : "?");                     \
     } while (0)
+
+// ---- host calls sharded over the members ---------------------------------------------------------------------------
+
+struct HostRange {
+    const void* p;
+    size_t bytes;
+};
+
+// The ranges one call page-locked: add() keeps a range only when mi::pin_host gave this call a reference, release() gives
+// back exactly those, once.  Only sharded_host_call holds one, and it releases behind its drain; the destructor is a backstop.
+class HostPins {
+public:
+    HostPins() = default;
+    HostPins(const HostPins&) = delete;
+    HostPins& operator=(const HostPins&) = delete;
+    ~HostPins() { release(); }
+    void add(const HostRange& h)
+    {
+        // a range beyond kMax stays pageable: its copies take hipMemcpyAsync's blocking path
+        if (count_ < kMax && mi::pin_host(h.p, h.bytes)) held_[count_++] = h.p;
+    }
+    void release()
+    {
+        for (int k = 0; k < count_; ++k) mi::unpin_host(held_[k]);
+        count_ = 0;
+    }
+
+private:
+    static constexpr int kMax = 4;
+    const void* held_[kMax];
+    int count_ = 0;
+};
+
+// scratch slots 0-2 of a member at the sizes its step needs (0: the slot is not used)
+mi_status grow_slots(mi_ctx* c, size_t bytes0, size_t bytes1, size_t bytes2)
+{
+    mi_status st = mi::ensure_scratch(c, 0, bytes0);
+    if (st == MI_OK) st = mi::ensure_scratch(c, 1, bytes1);
+    if (st == MI_OK) st = mi::ensure_scratch(c, 2, bytes2);
+    return st;
+}
+
+// The frame of every mi_group_*_host entry point (`who`).  `ranges` are page-locked when `pin`.  Members are visited in
+// rank order; member r gets [lo, hi) = mi_shard_bounds(count, r, P), one with an empty shard is skipped, and
+// enqueue(r, ctx, lo, hi, herr) runs with the member's device current: everything on the member's stream, nothing waits.
+// It returns a callee's status and leaves a failed copy in herr.  The first failure of either kind (or of hipSetDevice, a
+// copy error) ends the loop; afterwards(...), if given, is a second pass of the same shape that runs only when everything
+// before it succeeded.  Then every member's stream is drained, whatever happened, and only then the pins go.  Reported:
+// the callee's status with its own text, else the copy error, else the first failed synchronisation.
+// MI_TEST_FAIL_GROUP_SHARD (error-path test hook): a copy error instead of the second member that has work, with the
+// first one's copies and kernel enqueued.
+template <class Enqueue, class Afterwards = std::nullptr_t>
+mi_status sharded_host_call(mi_group* g, const char* who, size_t count, bool pin, std::initializer_list<HostRange> ranges,
+                            Enqueue enqueue, Afterwards afterwards = nullptr)
+{
+    const int P = (int)g->ctx.size();
+    HostPins pins;
+    if (pin)
+        for (const HostRange& h : ranges) pins.add(h);
+    mi_status st = MI_OK;
+    hipError_t herr = hipSuccess;
+    const char* what = "";
+    auto pass = [&](auto& step, bool fail_hook) {
+        int busy = 0;
+        for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
+            size_t lo, hi;
+            mi_shard_bounds(count, r, P, &lo, &hi);
+            if (hi == lo) continue;
+            if (fail_hook && busy++ == 1) { herr = hipErrorUnknown; what = "MI_TEST_FAIL_GROUP_SHARD (error-path test hook): "; break; }
+            herr = hipSetDevice(g->dev[r]);
+            if (herr == hipSuccess) st = step(r, g->ctx[r], lo, hi, herr);
+        }
+    };
+    pass(enqueue, getenv("MI_TEST_FAIL_GROUP_SHARD") != nullptr);
+    if constexpr (!std::is_same<Afterwards, std::nullptr_t>::value) pass(afterwards, false);
+    hipError_t esync = hipSuccess;
+    for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
+        (void)hipSetDevice(g->dev[r]);
+        const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
+        if (e != hipSuccess && esync == hipSuccess) esync = e;
+    }
+    pins.release();
+    if (st != MI_OK) return st;
+    if (herr != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "%s: copy failed: %s%s", who, what, hipGetErrorString(herr));
+    if (esync != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "%s: %s", who, hipGetErrorString(esync));
+    return MI_OK;
+}
 
 }  // namespace
 
@@ -341,40 +431,18 @@ mi_status mi_group_interp1_f64_host(mi_group* g, const mi_group_grid1* t, const 
     MI_REQUIRE(nullptr, t->g == g && t->grid.size() == g->ctx.size(), "mi_group_interp1_f64_host: the table belongs to another group");
     if (nq == 0) return MI_OK;
     MI_REQUIRE(nullptr, xq && yq, "mi_group_interp1_f64_host: NULL query/result pointer");
-    const int P = (int)g->ctx.size();
     // every shard: upload, kernel, download on its device's own stream; nothing waits until all are enqueued
-    const bool pin_in = mi::pin_host(xq, nq * sizeof(double)), pin_out = mi::pin_host(yq, nq * sizeof(double));
-    mi_status st = MI_OK;
-    hipError_t herr = hipSuccess;
-    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
-        size_t lo, hi;
-        mi_shard_bounds(nq, r, P, &lo, &hi);
-        if (hi == lo) continue;
-        mi_ctx* c = g->ctx[r];
-        herr = hipSetDevice(g->dev[r]);
-        if (herr != hipSuccess) break;
-        const size_t bytes = (hi - lo) * sizeof(double);
-        st = mi::ensure_scratch(c, 0, bytes);
-        if (st == MI_OK) st = mi::ensure_scratch(c, 1, bytes);
-        if (st != MI_OK) break;
-        herr = hipMemcpyAsync(c->scratch[0], xq + lo, bytes, hipMemcpyHostToDevice, c->stream);
-        if (herr != hipSuccess) break;
-        st = mi_interp1_f64_dev_v2(c, t->grid[r], (const double*)c->scratch[0], (double*)c->scratch[1], hi - lo, extrap);
-        if (st != MI_OK) break;
-        herr = hipMemcpyAsync(yq + lo, c->scratch[1], bytes, hipMemcpyDeviceToHost, c->stream);
-    }
-    hipError_t esync = hipSuccess;
-    for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
-        (void)hipSetDevice(g->dev[r]);
-        const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
-        if (e != hipSuccess && esync == hipSuccess) esync = e;
-    }
-    if (pin_in) mi::unpin_host(xq);
-    if (pin_out) mi::unpin_host(yq);
-    if (st != MI_OK) return st;
-    if (herr != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_f64_host: copy failed: %s", hipGetErrorString(herr));
-    if (esync != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_f64_host: %s", hipGetErrorString(esync));
-    return MI_OK;
+    return sharded_host_call(g, "mi_group_interp1_f64_host", nq, true, {{xq, nq * sizeof(double)}, {yq, nq * sizeof(double)}},
+        [&](int r, mi_ctx* c, size_t lo, size_t hi, hipError_t& herr) -> mi_status {
+            const size_t bytes = (hi - lo) * sizeof(double);
+            mi_status st = grow_slots(c, bytes, bytes, 0);
+            if (st != MI_OK) return st;
+            herr = hipMemcpyAsync(c->scratch[0], xq + lo, bytes, hipMemcpyHostToDevice, c->stream);
+            if (herr != hipSuccess) return MI_OK;
+            st = mi_interp1_f64_dev_v2(c, t->grid[r], (const double*)c->scratch[0], (double*)c->scratch[1], hi - lo, extrap);
+            if (st == MI_OK) herr = hipMemcpyAsync(yq + lo, c->scratch[1], bytes, hipMemcpyDeviceToHost, c->stream);
+            return st;
+        });
 }
 
 // ---- 2-D table interpolation (BASELINE config 3 over several GPUs: scattered query shards, the table replicated) ------
@@ -559,43 +627,20 @@ mi_status mi_group_interp2_f64_host(mi_group* g, const mi_group_grid2* t, const 
     MI_REQUIRE(nullptr, t->g == g && t->grid.size() == g->ctx.size(), "mi_group_interp2_f64_host: the table belongs to another group");
     if (nq == 0) return MI_OK;
     MI_REQUIRE(nullptr, xq && yq && zq, "mi_group_interp2_f64_host: NULL query/result pointer");
-    const int P = (int)g->ctx.size();
-    const bool pin_x = mi::pin_host(xq, nq * sizeof(double)), pin_y = mi::pin_host(yq, nq * sizeof(double)),
-               pin_z = mi::pin_host(zq, nq * sizeof(double));
-    mi_status st = MI_OK;
-    hipError_t herr = hipSuccess;
-    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
-        size_t lo, hi;
-        mi_shard_bounds(nq, r, P, &lo, &hi);
-        if (hi == lo) continue;
-        mi_ctx* c = g->ctx[r];
-        herr = hipSetDevice(g->dev[r]);
-        if (herr != hipSuccess) break;
-        const size_t bytes = (hi - lo) * sizeof(double);
-        for (int k = 0; k < 3 && st == MI_OK; ++k) st = mi::ensure_scratch(c, k, bytes);
-        if (st != MI_OK) break;
-        herr = hipMemcpyAsync(c->scratch[0], xq + lo, bytes, hipMemcpyHostToDevice, c->stream);
-        if (herr != hipSuccess) break;
-        herr = hipMemcpyAsync(c->scratch[1], yq + lo, bytes, hipMemcpyHostToDevice, c->stream);
-        if (herr != hipSuccess) break;
-        st = mi_interp2_f64_dev(c, t->grid[r], (const double*)c->scratch[0], (const double*)c->scratch[1], (double*)c->scratch[2],
-                                hi - lo, extrap);
-        if (st != MI_OK) break;
-        herr = hipMemcpyAsync(zq + lo, c->scratch[2], bytes, hipMemcpyDeviceToHost, c->stream);
-    }
-    hipError_t esync = hipSuccess;
-    for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
-        (void)hipSetDevice(g->dev[r]);
-        const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
-        if (e != hipSuccess && esync == hipSuccess) esync = e;
-    }
-    if (pin_x) mi::unpin_host(xq);
-    if (pin_y) mi::unpin_host(yq);
-    if (pin_z) mi::unpin_host(zq);
-    if (st != MI_OK) return st;
-    if (herr != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp2_f64_host: copy failed: %s", hipGetErrorString(herr));
-    if (esync != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp2_f64_host: %s", hipGetErrorString(esync));
-    return MI_OK;
+    const size_t all = nq * sizeof(double);
+    return sharded_host_call(g, "mi_group_interp2_f64_host", nq, true, {{xq, all}, {yq, all}, {zq, all}},
+        [&](int r, mi_ctx* c, size_t lo, size_t hi, hipError_t& herr) -> mi_status {
+            const size_t bytes = (hi - lo) * sizeof(double);
+            mi_status st = grow_slots(c, bytes, bytes, bytes);
+            if (st != MI_OK) return st;
+            herr = hipMemcpyAsync(c->scratch[0], xq + lo, bytes, hipMemcpyHostToDevice, c->stream);
+            if (herr == hipSuccess) herr = hipMemcpyAsync(c->scratch[1], yq + lo, bytes, hipMemcpyHostToDevice, c->stream);
+            if (herr != hipSuccess) return MI_OK;
+            st = mi_interp2_f64_dev(c, t->grid[r], (const double*)c->scratch[0], (const double*)c->scratch[1], (double*)c->scratch[2],
+                                    hi - lo, extrap);
+            if (st == MI_OK) herr = hipMemcpyAsync(zq + lo, c->scratch[2], bytes, hipMemcpyDeviceToHost, c->stream);
+            return st;
+        });
 }
 
 mi_status mi_group_interp2_grid_f64_host(mi_group* g, const mi_group_grid2* t, const double* xi, size_t nxi, const double* yi,
@@ -606,45 +651,21 @@ mi_status mi_group_interp2_grid_f64_host(mi_group* g, const mi_group_grid2* t, c
     if (nxi == 0 || nyi == 0) return MI_OK;
     MI_REQUIRE(nullptr, xi && yi && zi, "mi_group_interp2_grid_f64_host: NULL query/result pointer");
     MI_REQUIRE(nullptr, nxi <= SIZE_MAX / sizeof(double) / nyi, "mi_group_interp2_grid_f64_host: nxi=%zu x nyi=%zu too large", nxi, nyi);
-    const int P = (int)g->ctx.size();
-    const bool pin_x = mi::pin_host(xi, nxi * sizeof(double)), pin_y = mi::pin_host(yi, nyi * sizeof(double)),
-               pin_z = mi::pin_host(zi, nxi * nyi * sizeof(double));
-    mi_status st = MI_OK;
-    hipError_t herr = hipSuccess;
-    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
-        size_t lo, hi;
-        mi_shard_bounds(nxi, r, P, &lo, &hi);    // columns: one contiguous slice of the column-major zi
-        if (hi == lo) continue;
-        mi_ctx* c = g->ctx[r];
-        herr = hipSetDevice(g->dev[r]);
-        if (herr != hipSuccess) break;
-        const size_t m = hi - lo;
-        st = mi::ensure_scratch(c, 0, m * sizeof(double));
-        if (st == MI_OK) st = mi::ensure_scratch(c, 1, nyi * sizeof(double));
-        if (st == MI_OK) st = mi::ensure_scratch(c, 2, m * nyi * sizeof(double));
-        if (st != MI_OK) break;
-        herr = hipMemcpyAsync(c->scratch[0], xi + lo, m * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (herr != hipSuccess) break;
-        herr = hipMemcpyAsync(c->scratch[1], yi, nyi * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (herr != hipSuccess) break;
-        st = mi_interp2_grid_f64_dev(c, t->grid[r], (const double*)c->scratch[0], m, (const double*)c->scratch[1], nyi,
-                                     (double*)c->scratch[2], extrap);
-        if (st != MI_OK) break;
-        herr = hipMemcpyAsync(zi + lo * nyi, c->scratch[2], m * nyi * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    }
-    hipError_t esync = hipSuccess;
-    for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
-        (void)hipSetDevice(g->dev[r]);
-        const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
-        if (e != hipSuccess && esync == hipSuccess) esync = e;
-    }
-    if (pin_x) mi::unpin_host(xi);
-    if (pin_y) mi::unpin_host(yi);
-    if (pin_z) mi::unpin_host(zi);
-    if (st != MI_OK) return st;
-    if (herr != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp2_grid_f64_host: copy failed: %s", hipGetErrorString(herr));
-    if (esync != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp2_grid_f64_host: %s", hipGetErrorString(esync));
-    return MI_OK;
+    // the columns are sharded: member r's [lo, hi) is one contiguous slice of the column-major zi
+    return sharded_host_call(g, "mi_group_interp2_grid_f64_host", nxi, true,
+        {{xi, nxi * sizeof(double)}, {yi, nyi * sizeof(double)}, {zi, nxi * nyi * sizeof(double)}},
+        [&](int r, mi_ctx* c, size_t lo, size_t hi, hipError_t& herr) -> mi_status {
+            const size_t m = hi - lo;
+            mi_status st = grow_slots(c, m * sizeof(double), nyi * sizeof(double), m * nyi * sizeof(double));
+            if (st != MI_OK) return st;
+            herr = hipMemcpyAsync(c->scratch[0], xi + lo, m * sizeof(double), hipMemcpyHostToDevice, c->stream);
+            if (herr == hipSuccess) herr = hipMemcpyAsync(c->scratch[1], yi, nyi * sizeof(double), hipMemcpyHostToDevice, c->stream);
+            if (herr != hipSuccess) return MI_OK;
+            st = mi_interp2_grid_f64_dev(c, t->grid[r], (const double*)c->scratch[0], m, (const double*)c->scratch[1], nyi,
+                                         (double*)c->scratch[2], extrap);
+            if (st == MI_OK) herr = hipMemcpyAsync(zi + lo * nyi, c->scratch[2], m * nyi * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+            return st;
+        });
 }
 
 // interp1 over the columns of a matrix (mi_cols1.hip), columns sharded: member r takes [lo, hi) = mi_shard_bounds(ncols, r, P).
@@ -676,217 +697,109 @@ mi_status mi_group_interp1_cols_f64_host(mi_group* g, const double* x, size_t n,
         else if (ldy > SIZE_MAX / sizeof(double) / ncols || ldyi > SIZE_MAX / sizeof(double) / ncols)
             st = mi::fail(nullptr, MI_ERR_INVALID_ARG, "mi_group_interp1_cols_f64_host: ncols=%zu x (ldy=%zu, ldyi=%zu) too large", ncols, ldy, ldyi);
     }
-    if (st == MI_OK && ncols != 0 && nxi != 0) {
-        const bool pin_x = mi::pin_host(xi, nxi * sizeof(double)), pin_y = mi::pin_host(y, ((ncols - 1) * ldy + n) * sizeof(double)),
-                   pin_o = mi::pin_host(yi, ((ncols - 1) * ldyi + nxi) * sizeof(double));
-        hipError_t herr = hipSuccess;
-        for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
-            size_t lo, hi;
-            mi_shard_bounds(ncols, r, P, &lo, &hi);
-            if (hi == lo) continue;
-            mi_ctx* c = g->ctx[r];
-            herr = hipSetDevice(g->dev[r]);
-            if (herr != hipSuccess) break;
-            const size_t m = hi - lo;
-            st = mi::ensure_scratch(c, 0, nxi * sizeof(double));
-            if (st == MI_OK) st = mi::ensure_scratch(c, 1, m * n * sizeof(double));
-            if (st == MI_OK) st = mi::ensure_scratch(c, 2, m * nxi * sizeof(double));
-            if (st != MI_OK) break;
-            double *dxi = (double*)c->scratch[0], *dy = (double*)c->scratch[1], *dyi = (double*)c->scratch[2];
-            herr = hipMemcpyAsync(dxi, xi, nxi * sizeof(double), hipMemcpyHostToDevice, c->stream);
-            if (herr != hipSuccess) break;
-            herr = group_copy_cols(dy, n, y + lo * ldy, ldy, n, m, hipMemcpyHostToDevice, c->stream);
-            if (herr != hipSuccess) break;
-            st = mi_interp1_cols_f64_dev(c, axis[r], dy, n, m, dxi, nxi, dyi, nxi, extrap);
-            if (st != MI_OK) break;
-            herr = group_copy_cols(yi + lo * ldyi, ldyi, dyi, nxi, nxi, m, hipMemcpyDeviceToHost, c->stream);
-        }
-        hipError_t esync = hipSuccess;
-        for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
-            (void)hipSetDevice(g->dev[r]);
-            const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
-            if (e != hipSuccess && esync == hipSuccess) esync = e;
-        }
-        if (pin_x) mi::unpin_host(xi);
-        if (pin_y) mi::unpin_host(y);
-        if (pin_o) mi::unpin_host(yi);
-        if (st == MI_OK && herr != hipSuccess) st = mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_cols_f64_host: copy failed: %s", hipGetErrorString(herr));
-        if (st == MI_OK && esync != hipSuccess) st = mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_cols_f64_host: %s", hipGetErrorString(esync));
-    }
+    if (st == MI_OK && ncols != 0 && nxi != 0)
+        st = sharded_host_call(g, "mi_group_interp1_cols_f64_host", ncols, true,
+            {{xi, nxi * sizeof(double)}, {y, ((ncols - 1) * ldy + n) * sizeof(double)}, {yi, ((ncols - 1) * ldyi + nxi) * sizeof(double)}},
+            [&](int r, mi_ctx* c, size_t lo, size_t hi, hipError_t& herr) -> mi_status {
+                const size_t m = hi - lo;
+                mi_status s = grow_slots(c, nxi * sizeof(double), m * n * sizeof(double), m * nxi * sizeof(double));
+                if (s != MI_OK) return s;
+                double *dxi = (double*)c->scratch[0], *dy = (double*)c->scratch[1], *dyi = (double*)c->scratch[2];
+                herr = hipMemcpyAsync(dxi, xi, nxi * sizeof(double), hipMemcpyHostToDevice, c->stream);
+                if (herr == hipSuccess) herr = group_copy_cols(dy, n, y + lo * ldy, ldy, n, m, hipMemcpyHostToDevice, c->stream);
+                if (herr != hipSuccess) return MI_OK;
+                s = mi_interp1_cols_f64_dev(c, axis[r], dy, n, m, dxi, nxi, dyi, nxi, extrap);
+                if (s == MI_OK) herr = group_copy_cols(yi + lo * ldyi, ldyi, dyi, nxi, nxi, m, hipMemcpyDeviceToHost, c->stream);
+                return s;
+            });
     for (int r = 0; r < P; ++r) mi_axis1_destroy(axis[r]);
     return st;
 }
 
-// interp1 over paired columns (mi_pairs1.hip), columns sharded as above; XI is replicated.  Device copies are compact and
-// sub-allocated as in mi_interp1_pairs_f64_host: slot 0 the member's columns of X then of Y, slot 1 XI, len, col_ok,
-// slot 2 its columns of YI; slot 3 stays with the device call.
+// The two paired-column forms (`who`), columns sharded as above.  each_form: the call is mi_group_interp1_each_f64_host,
+// which has an ldxi to check and to name, and hands its shards to mi_interp1_each_f64_dev; pairs passes ldxi = 0.
+// Device copies are compact and sub-allocated as in the single-context host forms: slot 0 the member's columns of X then
+// of Y, slot 1 XI (one vector, or the member's columns when ldxi > 0), len, col_ok, slot 2 its columns of YI; slot 3
+// stays with the device call.
+static mi_status group_paired_host(mi_group* g, const char* who, bool each_form, const double* x, size_t ldx, const double* y,
+                                   size_t ldy, size_t n, const uint32_t* len, size_t ncols, const double* xi, size_t ldxi,
+                                   size_t nxi, double* yi, size_t ldyi, double extrap, uint32_t* col_ok)
+{
+    MI_REQUIRE(nullptr, g, "%s: NULL group", who);
+    if (ncols == 0 || nxi == 0) return MI_OK;
+    MI_REQUIRE(nullptr, x && y && xi && yi, "%s: NULL table/query/result pointer", who);
+    MI_REQUIRE(nullptr, n >= 2 && n < 0x7ffffff0u, "%s: need 2 <= n < 2^31 - 16 (n=%zu)", who, n);
+    MI_REQUIRE(nullptr, ldx >= n, "%s: ldx=%zu is smaller than n=%zu", who, ldx, n);
+    MI_REQUIRE(nullptr, ldy >= n, "%s: ldy=%zu is smaller than n=%zu", who, ldy, n);
+    MI_REQUIRE(nullptr, ldyi >= nxi, "%s: ldyi=%zu is smaller than nxi=%zu", who, ldyi, nxi);
+    const size_t lim = SIZE_MAX / (2 * sizeof(double)) / ncols;
+    const bool fits = ldx <= lim && ldy <= lim && ldyi <= lim && ldxi <= lim && nxi <= lim;
+    if (each_form) {
+        MI_REQUIRE(nullptr, ldxi == 0 || ldxi >= nxi, "%s: ldxi=%zu is smaller than nxi=%zu (0: one xi for every column)", who, ldxi, nxi);
+        MI_REQUIRE(nullptr, fits, "%s: ncols=%zu x (ldx=%zu, ldy=%zu, ldxi=%zu, ldyi=%zu) too large", who, ncols, ldx, ldy, ldxi, ldyi);
+    } else {
+        MI_REQUIRE(nullptr, fits, "%s: ncols=%zu x (ldx=%zu, ldy=%zu, ldyi=%zu) too large", who, ncols, ldx, ldy, ldyi);
+    }
+    const bool per_col = ldxi > 0;          // XI goes with its columns; otherwise one vector, replicated
+    std::vector<uint32_t> ok_own;
+    if (!col_ok) ok_own.resize(ncols);
+    uint32_t* const hok = col_ok ? col_ok : ok_own.data();
+    // the caller's arrays are page-locked above the size at which the single-context host forms start to chunk (2 x 8 M
+    // elements): below it registering four ranges costs more than the members' copies gain by overlapping, and the
+    // copies take hipMemcpyAsync's path for pageable memory
+    const bool big = std::max(n, nxi) > 2 * ((size_t)8 << 20) / ncols;
+    std::vector<const uint32_t*> dok_of(g->ctx.size(), nullptr);   // where each member's step put its col_ok
+    const mi_status st = sharded_host_call(g, who, ncols, big,
+        {{xi, ((ncols - 1) * ldxi + nxi) * sizeof(double)}, {x, ((ncols - 1) * ldx + n) * sizeof(double)},
+         {y, ((ncols - 1) * ldy + n) * sizeof(double)}, {yi, ((ncols - 1) * ldyi + nxi) * sizeof(double)}},
+        [&](int r, mi_ctx* c, size_t lo, size_t hi, hipError_t& herr) -> mi_status {
+            const size_t m = hi - lo, xi_bytes = (per_col ? m * nxi : nxi) * sizeof(double);
+            mi_status s = grow_slots(c, 2 * m * n * sizeof(double), xi_bytes + 2 * m * sizeof(uint32_t), m * nxi * sizeof(double));
+            if (s != MI_OK) return s;
+            double *dx = (double*)c->scratch[0], *dy = dx + m * n, *dxi = (double*)c->scratch[1], *dyi = (double*)c->scratch[2];
+            uint32_t *dlen = (uint32_t*)((char*)c->scratch[1] + xi_bytes), *dok = dlen + m;
+            dok_of[r] = dok;
+            if (per_col) herr = group_copy_cols(dxi, nxi, xi + lo * ldxi, ldxi, nxi, m, hipMemcpyHostToDevice, c->stream);
+            else herr = hipMemcpyAsync(dxi, xi, xi_bytes, hipMemcpyHostToDevice, c->stream);
+            if (herr == hipSuccess && len) herr = hipMemcpyAsync(dlen, len + lo, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+            if (herr == hipSuccess) herr = group_copy_cols(dx, n, x + lo * ldx, ldx, n, m, hipMemcpyHostToDevice, c->stream);
+            if (herr == hipSuccess) herr = group_copy_cols(dy, n, y + lo * ldy, ldy, n, m, hipMemcpyHostToDevice, c->stream);
+            if (herr != hipSuccess) return MI_OK;
+            if (each_form) s = mi_interp1_each_f64_dev(c, dx, n, dy, n, n, len ? dlen : nullptr, m, dxi, per_col ? nxi : 0, nxi, dyi, nxi, extrap, dok);
+            else s = mi_interp1_pairs_f64_dev(c, dx, n, dy, n, n, len ? dlen : nullptr, m, dxi, nxi, dyi, nxi, extrap, dok);
+            if (s == MI_OK) herr = group_copy_cols(yi + lo * ldyi, ldyi, dyi, nxi, nxi, m, hipMemcpyDeviceToHost, c->stream);
+            return s;
+        },
+        // the flags last: their host side is not pinned, so this copy waits for the member's stream
+        [&](int r, mi_ctx* c, size_t lo, size_t hi, hipError_t& herr) -> mi_status {
+            herr = hipMemcpyAsync(hok + lo, dok_of[r], (hi - lo) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+            return MI_OK;
+        });
+    if (st != MI_OK || col_ok) return st;
+    for (size_t c = 0; c < ncols; ++c)
+        if (!hok[c])
+            return mi::fail(nullptr, MI_ERR_GRID, "%s: column %zu is bad (len outside [2, n], or X not finite and strictly "
+                            "increasing; X is not sorted for the caller); its outputs are NaN", who, c);
+    return MI_OK;
+}
+
+// interp1 over paired columns (mi_pairs1.hip); XI is replicated
 mi_status mi_group_interp1_pairs_f64_host(mi_group* g, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
                                           const uint32_t* len, size_t ncols, const double* xi, size_t nxi, double* yi,
                                           size_t ldyi, double extrap, uint32_t* col_ok)
 {
-    MI_REQUIRE(nullptr, g, "mi_group_interp1_pairs_f64_host: NULL group");
-    if (ncols == 0 || nxi == 0) return MI_OK;
-    MI_REQUIRE(nullptr, x && y && xi && yi, "mi_group_interp1_pairs_f64_host: NULL table/query/result pointer");
-    MI_REQUIRE(nullptr, n >= 2 && n < 0x7ffffff0u, "mi_group_interp1_pairs_f64_host: need 2 <= n < 2^31 - 16 (n=%zu)", n);
-    MI_REQUIRE(nullptr, ldx >= n, "mi_group_interp1_pairs_f64_host: ldx=%zu is smaller than n=%zu", ldx, n);
-    MI_REQUIRE(nullptr, ldy >= n, "mi_group_interp1_pairs_f64_host: ldy=%zu is smaller than n=%zu", ldy, n);
-    MI_REQUIRE(nullptr, ldyi >= nxi, "mi_group_interp1_pairs_f64_host: ldyi=%zu is smaller than nxi=%zu", ldyi, nxi);
-    const size_t lim = SIZE_MAX / (2 * sizeof(double)) / ncols;
-    MI_REQUIRE(nullptr, ldx <= lim && ldy <= lim && ldyi <= lim && nxi <= lim,
-               "mi_group_interp1_pairs_f64_host: ncols=%zu x (ldx=%zu, ldy=%zu, ldyi=%zu) too large", ncols, ldx, ldy, ldyi);
-    const int P = (int)g->ctx.size();
-    std::vector<uint32_t> ok_own;
-    if (!col_ok) ok_own.resize(ncols);
-    uint32_t* const hok = col_ok ? col_ok : ok_own.data();
-    const size_t xi_bytes = nxi * sizeof(double);
-    // the caller's arrays are page-locked above the size at which mi_interp1_pairs_f64_host starts to chunk (2 x 8 M
-    // elements): below it registering four ranges costs more than the members' copies gain by overlapping, and the
-    // copies take hipMemcpyAsync's path for pageable memory
-    const bool big = std::max(n, nxi) > 2 * ((size_t)8 << 20) / ncols;
-    const bool pin_q = big && mi::pin_host(xi, xi_bytes), pin_x = big && mi::pin_host(x, ((ncols - 1) * ldx + n) * sizeof(double)),
-               pin_y = big && mi::pin_host(y, ((ncols - 1) * ldy + n) * sizeof(double)),
-               pin_o = big && mi::pin_host(yi, ((ncols - 1) * ldyi + nxi) * sizeof(double));
-    mi_status st = MI_OK;
-    hipError_t herr = hipSuccess;
-    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
-        size_t lo, hi;
-        mi_shard_bounds(ncols, r, P, &lo, &hi);
-        if (hi == lo) continue;
-        mi_ctx* c = g->ctx[r];
-        herr = hipSetDevice(g->dev[r]);
-        if (herr != hipSuccess) break;
-        const size_t m = hi - lo;
-        st = mi::ensure_scratch(c, 0, 2 * m * n * sizeof(double));
-        if (st == MI_OK) st = mi::ensure_scratch(c, 1, xi_bytes + 2 * m * sizeof(uint32_t));
-        if (st == MI_OK) st = mi::ensure_scratch(c, 2, m * nxi * sizeof(double));
-        if (st != MI_OK) break;
-        double *dx = (double*)c->scratch[0], *dy = dx + m * n, *dxi = (double*)c->scratch[1], *dyi = (double*)c->scratch[2];
-        uint32_t *dlen = (uint32_t*)((char*)c->scratch[1] + xi_bytes), *dok = dlen + m;
-        herr = hipMemcpyAsync(dxi, xi, xi_bytes, hipMemcpyHostToDevice, c->stream);
-        if (herr == hipSuccess && len) herr = hipMemcpyAsync(dlen, len + lo, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (herr == hipSuccess) herr = group_copy_cols(dx, n, x + lo * ldx, ldx, n, m, hipMemcpyHostToDevice, c->stream);
-        if (herr == hipSuccess) herr = group_copy_cols(dy, n, y + lo * ldy, ldy, n, m, hipMemcpyHostToDevice, c->stream);
-        if (herr != hipSuccess) break;
-        st = mi_interp1_pairs_f64_dev(c, dx, n, dy, n, n, len ? dlen : nullptr, m, dxi, nxi, dyi, nxi, extrap, dok);
-        if (st != MI_OK) break;
-        herr = group_copy_cols(yi + lo * ldyi, ldyi, dyi, nxi, nxi, m, hipMemcpyDeviceToHost, c->stream);
-    }
-    // the flags last: their host side is not pinned, so this copy waits for the member's stream
-    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
-        size_t lo, hi;
-        mi_shard_bounds(ncols, r, P, &lo, &hi);
-        if (hi == lo) continue;
-        herr = hipSetDevice(g->dev[r]);
-        const uint32_t* dok = (const uint32_t*)((const char*)g->ctx[r]->scratch[1] + xi_bytes) + (hi - lo);
-        if (herr == hipSuccess) herr = hipMemcpyAsync(hok + lo, dok, (hi - lo) * sizeof(uint32_t), hipMemcpyDeviceToHost, g->ctx[r]->stream);
-    }
-    hipError_t esync = hipSuccess;
-    for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
-        (void)hipSetDevice(g->dev[r]);
-        const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
-        if (e != hipSuccess && esync == hipSuccess) esync = e;
-    }
-    if (pin_q) mi::unpin_host(xi);
-    if (pin_x) mi::unpin_host(x);
-    if (pin_y) mi::unpin_host(y);
-    if (pin_o) mi::unpin_host(yi);
-    if (st != MI_OK) return st;
-    if (herr != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_pairs_f64_host: copy failed: %s", hipGetErrorString(herr));
-    if (esync != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_pairs_f64_host: %s", hipGetErrorString(esync));
-    if (!col_ok)
-        for (size_t c = 0; c < ncols; ++c)
-            if (!hok[c])
-                return mi::fail(nullptr, MI_ERR_GRID, "mi_group_interp1_pairs_f64_host: column %zu is bad (len outside [2, n], or X not "
-                                "finite and strictly increasing; X is not sorted for the caller); its outputs are NaN", c);
-    return MI_OK;
+    return group_paired_host(g, "mi_group_interp1_pairs_f64_host", false, x, ldx, y, ldy, n, len, ncols, xi, 0, nxi, yi, ldyi, extrap,
+                             col_ok);
 }
 
-// interp1 over paired columns with a query vector per column (mi_each1.hip), columns sharded as above; XI goes with its
-// columns when ldxi > 0 and is replicated when ldxi == 0.  Slots as in mi_interp1_each_f64_host: slot 0 the member's
-// columns of X then of Y, slot 1 XI (one vector, or the member's columns), len, col_ok, slot 2 its columns of YI.
+// interp1 over paired columns with a query vector per column (mi_each1.hip); XI goes with its columns when ldxi > 0 and is
+// replicated when ldxi == 0
 mi_status mi_group_interp1_each_f64_host(mi_group* g, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
                                          const uint32_t* len, size_t ncols, const double* xi, size_t ldxi, size_t nxi,
                                          double* yi, size_t ldyi, double extrap, uint32_t* col_ok)
 {
-    MI_REQUIRE(nullptr, g, "mi_group_interp1_each_f64_host: NULL group");
-    if (ncols == 0 || nxi == 0) return MI_OK;
-    MI_REQUIRE(nullptr, x && y && xi && yi, "mi_group_interp1_each_f64_host: NULL table/query/result pointer");
-    MI_REQUIRE(nullptr, n >= 2 && n < 0x7ffffff0u, "mi_group_interp1_each_f64_host: need 2 <= n < 2^31 - 16 (n=%zu)", n);
-    MI_REQUIRE(nullptr, ldx >= n, "mi_group_interp1_each_f64_host: ldx=%zu is smaller than n=%zu", ldx, n);
-    MI_REQUIRE(nullptr, ldy >= n, "mi_group_interp1_each_f64_host: ldy=%zu is smaller than n=%zu", ldy, n);
-    MI_REQUIRE(nullptr, ldyi >= nxi, "mi_group_interp1_each_f64_host: ldyi=%zu is smaller than nxi=%zu", ldyi, nxi);
-    MI_REQUIRE(nullptr, ldxi == 0 || ldxi >= nxi, "mi_group_interp1_each_f64_host: ldxi=%zu is smaller than nxi=%zu (0: one xi for every column)", ldxi, nxi);
-    const size_t lim = SIZE_MAX / (2 * sizeof(double)) / ncols;
-    MI_REQUIRE(nullptr, ldx <= lim && ldy <= lim && ldyi <= lim && ldxi <= lim && nxi <= lim,
-               "mi_group_interp1_each_f64_host: ncols=%zu x (ldx=%zu, ldy=%zu, ldxi=%zu, ldyi=%zu) too large", ncols, ldx, ldy, ldxi, ldyi);
-    const int P = (int)g->ctx.size();
-    const bool each = ldxi > 0;
-    std::vector<uint32_t> ok_own;
-    if (!col_ok) ok_own.resize(ncols);
-    uint32_t* const hok = col_ok ? col_ok : ok_own.data();
-    // page-locked above the size at which mi_interp1_each_f64_host starts to chunk, as mi_group_interp1_pairs_f64_host
-    const bool big = std::max(n, nxi) > 2 * ((size_t)8 << 20) / ncols;
-    const bool pin_q = big && mi::pin_host(xi, ((ncols - 1) * ldxi + nxi) * sizeof(double)),
-               pin_x = big && mi::pin_host(x, ((ncols - 1) * ldx + n) * sizeof(double)),
-               pin_y = big && mi::pin_host(y, ((ncols - 1) * ldy + n) * sizeof(double)),
-               pin_o = big && mi::pin_host(yi, ((ncols - 1) * ldyi + nxi) * sizeof(double));
-    mi_status st = MI_OK;
-    hipError_t herr = hipSuccess;
-    std::vector<size_t> q_bytes(P, 0);      // bytes of XI in front of len and col_ok in each member's slot 1
-    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
-        size_t lo, hi;
-        mi_shard_bounds(ncols, r, P, &lo, &hi);
-        if (hi == lo) continue;
-        mi_ctx* c = g->ctx[r];
-        herr = hipSetDevice(g->dev[r]);
-        if (herr != hipSuccess) break;
-        const size_t m = hi - lo;
-        const size_t xi_bytes = (each ? m * nxi : nxi) * sizeof(double);
-        q_bytes[r] = xi_bytes;
-        st = mi::ensure_scratch(c, 0, 2 * m * n * sizeof(double));
-        if (st == MI_OK) st = mi::ensure_scratch(c, 1, xi_bytes + 2 * m * sizeof(uint32_t));
-        if (st == MI_OK) st = mi::ensure_scratch(c, 2, m * nxi * sizeof(double));
-        if (st != MI_OK) break;
-        double *dx = (double*)c->scratch[0], *dy = dx + m * n, *dxi = (double*)c->scratch[1], *dyi = (double*)c->scratch[2];
-        uint32_t *dlen = (uint32_t*)((char*)c->scratch[1] + xi_bytes), *dok = dlen + m;
-        if (each) herr = group_copy_cols(dxi, nxi, xi + lo * ldxi, ldxi, nxi, m, hipMemcpyHostToDevice, c->stream);
-        else herr = hipMemcpyAsync(dxi, xi, xi_bytes, hipMemcpyHostToDevice, c->stream);
-        if (herr == hipSuccess && len) herr = hipMemcpyAsync(dlen, len + lo, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (herr == hipSuccess) herr = group_copy_cols(dx, n, x + lo * ldx, ldx, n, m, hipMemcpyHostToDevice, c->stream);
-        if (herr == hipSuccess) herr = group_copy_cols(dy, n, y + lo * ldy, ldy, n, m, hipMemcpyHostToDevice, c->stream);
-        if (herr != hipSuccess) break;
-        st = mi_interp1_each_f64_dev(c, dx, n, dy, n, n, len ? dlen : nullptr, m, dxi, each ? nxi : 0, nxi, dyi, nxi, extrap, dok);
-        if (st != MI_OK) break;
-        herr = group_copy_cols(yi + lo * ldyi, ldyi, dyi, nxi, nxi, m, hipMemcpyDeviceToHost, c->stream);
-    }
-    // the flags last: their host side is not pinned, so this copy waits for the member's stream
-    for (int r = 0; r < P && st == MI_OK && herr == hipSuccess; ++r) {
-        size_t lo, hi;
-        mi_shard_bounds(ncols, r, P, &lo, &hi);
-        if (hi == lo) continue;
-        herr = hipSetDevice(g->dev[r]);
-        const uint32_t* dok = (const uint32_t*)((const char*)g->ctx[r]->scratch[1] + q_bytes[r]) + (hi - lo);
-        if (herr == hipSuccess) herr = hipMemcpyAsync(hok + lo, dok, (hi - lo) * sizeof(uint32_t), hipMemcpyDeviceToHost, g->ctx[r]->stream);
-    }
-    hipError_t esync = hipSuccess;
-    for (int r = 0; r < P; ++r) {   // drain every stream before the ranges are released, on success or error
-        (void)hipSetDevice(g->dev[r]);
-        const hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);
-        if (e != hipSuccess && esync == hipSuccess) esync = e;
-    }
-    if (pin_q) mi::unpin_host(xi);
-    if (pin_x) mi::unpin_host(x);
-    if (pin_y) mi::unpin_host(y);
-    if (pin_o) mi::unpin_host(yi);
-    if (st != MI_OK) return st;
-    if (herr != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_each_f64_host: copy failed: %s", hipGetErrorString(herr));
-    if (esync != hipSuccess) return mi::fail(nullptr, MI_ERR_HIP, "mi_group_interp1_each_f64_host: %s", hipGetErrorString(esync));
-    if (!col_ok)
-        for (size_t c = 0; c < ncols; ++c)
-            if (!hok[c])
-                return mi::fail(nullptr, MI_ERR_GRID, "mi_group_interp1_each_f64_host: column %zu is bad (len outside [2, n], or X not "
-                                "finite and strictly increasing; X is not sorted for the caller); its outputs are NaN", c);
-    return MI_OK;
+    return group_paired_host(g, "mi_group_interp1_each_f64_host", true, x, ldx, y, ldy, n, len, ncols, xi, ldxi, nxi, yi, ldyi, extrap,
+                             col_ok);
 }
 
 // ---- EventDrivenMap -----------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Edge sweep of the multi-GPU layer's original entry points (csrc/mi_group.hip): mi_group_interp1_f64_dev with and without
 the (chunked) gather at every (n_per_shard, K) of tests/group_cases.py, mi_group_interp2_f64_dev's gather in place and out
 of place, the host forms at query counts that leave members without work, two calls back to back without a
-synchronisation in between, every documented error, and group EDM at the smallest shard sizes.
+synchronisation in between, every documented error, the six sharded host forms under a failure injected at the second
+member (MI_TEST_FAIL_GROUP_SHARD), and group EDM at the smallest shard sizes.
 
 Groups: GPU 0 named one, two, three and five times (a rehearsal group: device-to-device copies instead of RCCL), and every
 device of the machine ([0] on a single-GPU one: the RCCL binding with one rank).  One group is alive at a time.  Every
@@ -338,6 +339,67 @@ def test_errors_name_their_function_and_leave_the_group_usable(rig):
     assert e.value.code == 1 and "mi_group_edm" in str(e.value)
     _still_works(rig)
     assert L.mi_debug_pinned_ranges() == 0
+
+
+def _host_form_calls(rig, mi_ctx):
+    """(entry point, call, expected) for the six sharded host forms at the smallest shapes that give two members work: 4097
+    queries for interp1 / interp2, 2P + 1 columns for the others (n = 5, nxi = 9; nyi = 5).  Expected: the oracle for
+    interp1 / interp2, the single-context device call for the column forms"""
+    import armadillocudalinearinterpolation_amd as mi
+    grp, P = rig["grp"], rig["P"]
+    x, y, z = gc.table2()
+    q, q2 = gc.queries(7200, 4097), gc.queries(7201, 4097)[::-1].copy()
+    B, n, nxi = 2 * P + 1, 5, 9
+    gx, gy = gc.queries(7202, B), gc.queries(7203, 5)
+    Xb = np.cumsum(0.25 + oracle.splitmix_uniform(7204, B * n).reshape(B, n), axis=1)      # a strictly increasing X per column
+    Yb = oracle.splitmix_uniform(7205, B * n).reshape(B, n) + 2.0
+    xi = Xb[0, 0] + gc.queries(7206, nxi) * (Xb[0, -1] - Xb[0, 0])
+    Q = Xb[:, :1] + gc.queries(7207, B * nxi).reshape(B, nxi) * (Xb[:, -1:] - Xb[:, :1])
+    axis = mi.Axis1.from_nodes(mi_ctx, Xb[0])
+    host = lambda t: t.cpu().numpy()                           # noqa: E731
+    calls = [
+        ("mi_group_interp1_f64_host", lambda: rig["nonuniform"].interp_host(q, extrap=-2.5), _ref1("nonuniform", q, -2.5)),
+        ("mi_group_interp2_f64_host", lambda: rig["grid2"].interp_host(q, q2, extrap=7.0),
+         oracle.interp2_bilinear(x, y, z, q, q2, extrap=7.0)),
+        ("mi_group_interp2_grid_f64_host", lambda: rig["grid2"].interp_grid_host(gx, gy, extrap=7.0),
+         host(rig["one_grid2"].interp_grid(_t(gx), _t(gy), extrap=7.0))),
+        ("mi_group_interp1_cols_f64_host", lambda: grp.interp_cols_host(Xb[0], Yb.T, xi, extrap=-4.0),
+         host(axis.interp_cols(_t(Yb).T, _t(xi), extrap=-4.0))),
+        ("mi_group_interp1_pairs_f64_host", lambda: grp.interp_pairs_host(Xb.T, Yb.T, xi, extrap=-4.0),
+         host(mi.interp_pairs(mi_ctx, _t(Xb).T, _t(Yb).T, _t(xi), extrap=-4.0))),
+        ("mi_group_interp1_each_f64_host", lambda: grp.interp_each_host(Xb.T, Yb.T, Q.T, extrap=-4.0),
+         host(mi.interp_each(mi_ctx, _t(Xb).T, _t(Yb).T, _t(Q).T, extrap=-4.0))),
+        ("mi_group_interp1_each_f64_host", lambda: grp.interp_each_host(Xb.T, Yb.T, xi, extrap=-4.0),
+         host(mi.interp_each(mi_ctx, _t(Xb).T, _t(Yb).T, _t(xi), extrap=-4.0))),
+    ]
+    axis.close()
+    return calls
+
+
+@every_group
+def test_host_forms_failing_at_the_second_member_release_their_pins(rig, mi_ctx, monkeypatch):
+    """MI_TEST_FAIL_GROUP_SHARD makes the shard loop fail in place of the second member that has work, with the first one's
+    copies and kernel enqueued: every host form reports MI_ERR_HIP naming itself and the hook, and no range stays
+    page-locked (the streams were drained and the pins given back).  A group of one member never trips the hook.  With the
+    variable gone the same calls on the same group give the expected bits."""
+    import armadillocudalinearinterpolation_amd as mi
+    P, L = rig["P"], rig["L"]
+    calls = _host_form_calls(rig, mi_ctx)
+    assert L.mi_debug_pinned_ranges() == 0
+    monkeypatch.setenv("MI_TEST_FAIL_GROUP_SHARD", "1")
+    for who, call, want in calls:
+        if P == 1:
+            assert gc.same_bits(call(), want), who
+        else:
+            with pytest.raises(mi.MiError) as e:
+                call()
+            assert e.value.code == 3 and who + ":" in str(e.value) and "MI_TEST_FAIL_GROUP_SHARD" in str(e.value), who
+        assert L.mi_debug_pinned_ranges() == 0, who
+    monkeypatch.delenv("MI_TEST_FAIL_GROUP_SHARD")
+    for who, call, want in calls:
+        assert gc.same_bits(call(), want), who
+        assert L.mi_debug_pinned_ranges() == 0, who
+    _still_works(rig)
 
 
 # ---- group EDM at the smallest shard sizes ---------------------------------------------------------------------------
