@@ -32,3 +32,9 @@ def test_edm_fuzz_short(mi_ctx, monkeypatch):
     monkeypatch.delenv("MI_EDM_WAVES_PER_REALISATION", raising=False)
     res = _load("gpu_fuzz_edm").run(10.0, 2024, ctx=mi_ctx)
     assert res["cases"] >= 30 and res["filled"] >= 3         # (filled: launches of 3200 realisations, more than the device holds at once)
+
+
+def test_batched_fuzz_short(mi_ctx):
+    res = _load("gpu_fuzz_batched").run(10.0, 2024, ctx=mi_ctx)
+    assert set(res["forms"]) == {"cols", "rows", "stack", "pairs", "each", "rowpairs", "grid", "slices2"}
+    assert all(len(forms) >= 2 for forms in res["forms"].values()), res["forms"]     # every call ran, in two forms at least
