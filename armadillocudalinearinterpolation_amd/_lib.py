@@ -53,6 +53,7 @@ SIGNATURES = {
     "mi_debug_slices2_launches": (_sz, [_i32]),
     "mi_debug_rows1_launches": (_sz, [_i32]),
     "mi_debug_rowpairs_launches": (_sz, [_i32]),
+    "mi_debug_nearest_launches": (_sz, [_i32]),
     "mi_debug_grid1_formula": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "mi_last_error": (C.c_char_p, [_vp]),
     "mi_ctx_create": (_i32, [_i32, _pp]),
@@ -75,6 +76,9 @@ SIGNATURES = {
     "mi_interp1_f64_dev_v2": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
     "mi_interp1_f64_host": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
     "mi_interp1_f64": (_i32, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _dbl]),
+    "mi_interp1_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
+    "mi_interp1_nearest_f64_host": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
+    "mi_interp1_nearest_f64": (_i32, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _dbl]),
     "mi_grid2_create": (_i32, [_vp, _vp, _sz, _vp, _sz, _vp, C.c_uint, _pp]),
     "mi_grid2_create_uniform": (_i32, [_vp, _dbl, _dbl, _sz, _dbl, _dbl, _sz, _vp, C.c_uint, _pp]),
     "mi_grid2_destroy": (_i32, [_vp]),
@@ -88,6 +92,7 @@ SIGNATURES = {
     "mi_axis1_destroy": (_i32, [_vp]),
     "mi_interp1_cols_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
     "mi_interp1_cols_f64_host": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
+    "mi_interp1_cols_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
     "mi_interp1_pairs_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp1_pairs_f64_host": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp1_each_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _dbl, _vp]),

@@ -289,6 +289,32 @@ class Grid1:
               self._ctx._h)
         return out
 
+    def interp_nearest(self, xq, out=None, extrap=math.nan):
+        """arma::interp1's "nearest" method on this table: out[i] = Y[k], k the node nearest to xq[i] (a tie keeps the
+        left node; the stored value comes back as it is).  xq: contiguous float64 CUDA tensor; asynchronous on the
+        context's stream."""
+        _need_f64_cuda(xq, "xq", True)
+        if out is None:
+            out = _torch().empty_like(xq)
+        else:
+            _need_f64_cuda(out, "out", True, "out must be a contiguous float64 CUDA tensor of the same size")
+            if out.numel() != xq.numel():
+                raise ValueError("out must be a contiguous float64 CUDA tensor of the same size")
+        check(self._L.mi_interp1_nearest_f64_dev(self._ctx._h, self._h, _ptr(xq), _ptr(out), xq.numel(), float(extrap)),
+              self._ctx._h)
+        return out
+
+    def interp_nearest_host(self, xq, extrap=math.nan, out=None):
+        """interp_nearest on host arrays (synchronous)"""
+        xq = _np64(xq)
+        if out is None:
+            out = np.empty_like(xq)
+        elif out.dtype != np.float64 or out.size != xq.size or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("out must be a contiguous float64 array of the query size")
+        check(self._L.mi_interp1_nearest_f64_host(self._ctx._h, self._h, _ptr(xq), _ptr(out), xq.size, float(extrap)),
+              self._ctx._h)
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.mi_grid1_destroy(self._h)
@@ -308,6 +334,17 @@ def interp1(ctx, X, Y, XI, extrap=math.nan):
         raise ValueError("X and Y must have the same number of elements")
     YI = np.empty_like(XI)
     check(ctx._L.mi_interp1_f64(ctx._h, _ptr(X), _ptr(Y), X.size, _ptr(XI), _ptr(YI), XI.size, float(extrap)), ctx._h)
+    return YI
+
+
+def interp1_nearest(ctx, X, Y, XI, extrap=math.nan):
+    """arma::interp1(X, Y, XI, YI, "nearest", extrap) on host arrays (X sorted and de-duplicated first), on the GPU."""
+    X, Y, XI = _np64(X), _np64(Y), _np64(XI)
+    if X.size != Y.size:
+        raise ValueError("X and Y must have the same number of elements")
+    YI = np.empty_like(XI)
+    check(ctx._L.mi_interp1_nearest_f64(ctx._h, _ptr(X), _ptr(Y), X.size, _ptr(XI), _ptr(YI), XI.size, float(extrap)),
+          ctx._h)
     return YI
 
 
@@ -478,6 +515,18 @@ class Axis1(_Handle):
         out, ldyi = _out_colmajor(out, nxi, B, Y)
         check(self._L.mi_interp1_cols_f64_dev(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, B, _ptr(xi), nxi,
                                               C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
+        return out
+
+    def interp_cols_nearest(self, Y, xi, out=None, extrap=math.nan):
+        """interp_cols with arma::interp1's "nearest" method: out[i, c] = Y[k, c], k the node nearest to xi[i] (a tie
+        keeps the left node; the stored value comes back as it is).  Arguments and layouts as interp_cols."""
+        _need_f64_cuda(xi, "xi", True)
+        _need_f64_cuda(Y, "Y", False)
+        ldy, B = self._colmajor_view(Y, self.n, "Y")
+        nxi = xi.numel()
+        out, ldyi = _out_colmajor(out, nxi, B, Y)
+        check(self._L.mi_interp1_cols_nearest_f64_dev(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, B, _ptr(xi), nxi,
+                                                      C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
         return out
 
     @staticmethod

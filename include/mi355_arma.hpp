@@ -3,7 +3,10 @@
 // out, as BASELINE.json's north_star asks.  Header-only; link libmi355interp.so.
 //
 //   mi355::interp1(X, Y, XI, YI)            == arma::interp1(X, Y, XI, YI, "linear")
+//   mi355::interp1(X, Y, XI, YI, method)    == arma::interp1(X, Y, XI, YI, method): "linear", "*linear", "nearest",
+//                                           "*nearest" (the starred forms take X as given: strictly increasing, else throw)
 //   mi355::Interp1Table tab(X, Y); tab(XI, YI)   table resident in HBM across calls
+//                       tab.nearest(XI, YI)      the "nearest" method on the same resident table
 //   mi355::interp1(X, Y, XI, YI)            Y, YI arma::mat: interp1 on every column of Y (MATLAB's interp1 with a matrix
 //                                           Y), YI = XI.n_elem x Y.n_cols; X as given ("*linear": strictly increasing)
 //   mi355::Interp1Axis ax(X); ax(Y, XI, YI)      the axis resident across calls while Y changes
@@ -34,6 +37,7 @@
 #include <stdexcept>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mi355_arma_compat.hpp"
@@ -96,6 +100,15 @@ class Interp1Table {
               "mi_interp1_f64_host");
     }
 
+    // arma::interp1's "nearest" method on the same resident table: YI[i] = Y[k], k the node nearest to XI[i]
+    // (a tie keeps the left node; the stored value comes back as it is)
+    void nearest(const arma::vec& XI, arma::vec& YI, double extrap_val = std::numeric_limits<double>::quiet_NaN()) const
+    {
+        YI.set_size(XI.n_elem);
+        check(mi_interp1_nearest_f64_host(dev_.get(), g_, XI.memptr(), YI.memptr(), XI.n_elem, extrap_val), dev_.get(),
+              "mi_interp1_nearest_f64_host");
+    }
+
   private:
     Device& dev_;
     mi_grid1* g_;
@@ -109,6 +122,35 @@ inline void interp1(const arma::vec& X, const arma::vec& Y, const arma::vec& XI,
     YI.set_size(XI.n_elem);
     check(mi_interp1_f64(dev.get(), X.memptr(), Y.memptr(), X.n_elem, XI.memptr(), YI.memptr(), XI.n_elem, extrap_val),
           dev.get(), "mi_interp1_f64");
+}
+
+// arma::interp1(X, Y, XI, YI, method, extrap_val) with Armadillo's four method strings:
+//   "linear"    X sorted and de-duplicated first, the fp64 blend             (mi_interp1_f64, as the overload above)
+//   "*linear"   X used as given, must be strictly increasing (else throws)   (mi_interp1_f64_host)
+//   "nearest"   X sorted and de-duplicated first, the nearest rule           (mi_interp1_nearest_f64)
+//   "*nearest"  X used as given, must be strictly increasing (else throws)   (mi_interp1_nearest_f64_host)
+// anything else throws std::invalid_argument, as Armadillo does.
+inline void interp1(const arma::vec& X, const arma::vec& Y, const arma::vec& XI, arma::vec& YI, const char* method,
+                    double extrap_val = std::numeric_limits<double>::quiet_NaN(), Device& dev = Device::instance())
+{
+    const std::string m = method ? method : "";
+    if (m == "linear") return interp1(X, Y, XI, YI, extrap_val, dev);
+    if (m == "*linear") return Interp1Table(X, Y, false, dev)(XI, YI, extrap_val);
+    if (m == "*nearest") return Interp1Table(X, Y, false, dev).nearest(XI, YI, extrap_val);
+    if (m != "nearest") throw std::invalid_argument("interp1(): unsupported interpolation type");
+    if (X.n_elem != Y.n_elem) throw std::invalid_argument("interp1(): X and Y must have the same number of elements");
+    YI.set_size(XI.n_elem);
+    check(mi_interp1_nearest_f64(dev.get(), X.memptr(), Y.memptr(), X.n_elem, XI.memptr(), YI.memptr(), XI.n_elem, extrap_val),
+          dev.get(), "mi_interp1_nearest_f64");
+}
+
+// an integer extrapolation value (a literal 0 among them) still means the linear overload: without this the null
+// pointer conversion to `const char* method` would compete with the conversion to double
+template <typename T, typename std::enable_if<std::is_integral<T>::value, int>::type = 0>
+inline void interp1(const arma::vec& X, const arma::vec& Y, const arma::vec& XI, arma::vec& YI, T extrap_val,
+                    Device& dev = Device::instance())
+{
+    interp1(X, Y, XI, YI, (double)extrap_val, dev);
 }
 
 // interp1 over the columns of a matrix: YI(:, c) = arma::interp1(X, Y.col(c), XI, YI.col(c), "*linear", extrap_val) for

@@ -32,6 +32,24 @@
  *        a = q - X[l];  b = X[r] - q;  w = a > 0 ? a/(a+b) : 0
  *        out = (1-w)*Y[l] + w*Y[r]          (every op rounded, no FMA)
  *     q < X[0] or q > X[n-1] -> extrap_val;  q = NaN -> NaN.
+ *   - nearest rule shared by every "nearest" entry point (arma::interp1's
+ *     "nearest" / "*nearest", interp1_helper_nearest):
+ *        q = NaN                   -> NaN
+ *        q < X[0] or q > X[n-1]    -> extrap_val
+ *        otherwise   l = largest node with X[l] <= q,  r = min(l+1, n-1)      (the blend's bracket)
+ *                    a = q - X[l];  b = X[r] - q        (one rounded fp64 subtraction each)
+ *                    k = (b < a) ? r : l                (a tie keeps the LEFT node)
+ *                    out = Y[k]                          (a copy: no arithmetic touches the value)
+ *     inf, -0.0, denormals and NaN in Y come back exactly as stored, and only for
+ *     queries whose nearest node holds them.  The decision comes from a and b
+ *     themselves, never from the blend's weight a/(a+b), which rounds and can equal
+ *     0.5 when a != b.  Armadillo scans the nodes and stops at the first error that
+ *     does not decrease (err >= best_err), which also keeps the left node of a tie;
+ *     the rule equals that scan whenever fl(|X[j]-q|) strictly decreases along it.
+ *     The one deviation: where two nodes in front of the nearest one are so close
+ *     that their rounded distances to q are equal (X = [0, 2^-60, 1, 2], q = 1:
+ *     1 - 0 and 1 - 2^-60 round to the same double) the scan stops there (node 0)
+ *     and the rule returns the true nearest node (node 2).  DESIGN.md section 2.
  */
 #ifndef MI355_INTERP_H
 #define MI355_INTERP_H
@@ -62,7 +80,11 @@ extern "C" {
  *                the rows of a matrix / across the slices of a cube: one X, a table per row; device form only);
  *                mi_interp1_rowpairs_f64_dev, mi_debug_rowpairs_launches (interp1 over paired rows: every row of Y with
  *                its own X, realisation-fastest data; device form only);
- *                mi_group_wait_stream (a group member's stream behind a stream of the caller's) */
+ *                mi_group_wait_stream (a group member's stream behind a stream of the caller's);
+ *                mi_interp1_nearest_f64_dev, mi_interp1_nearest_f64_host, mi_interp1_nearest_f64,
+ *                mi_interp1_cols_nearest_f64_dev, mi_debug_nearest_launches (arma::interp1's "nearest" method: table
+ *                lookup on the mi_grid1 handles of the linear calls, and the columns of a matrix; device form only
+ *                for the columns) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -113,6 +135,10 @@ size_t mi_debug_rows1_launches(int form);
 /* Test hook: calls of mi_interp1_rowpairs_f64_dev by this process so far that took the given form: 0 short-row form
  * (n <= 32, one launch), 1 long-row form (validation pass, then the march); 0 for any other value of form. */
 size_t mi_debug_rowpairs_launches(int form);
+/* Test hook: calls of the nearest entry points by this process so far that took the given form: 0 streaming kernel,
+ * 1 whole table in LDS, 2 scalar kernel (pointers not 16-B aligned) -- mi_interp1_nearest_f64_dev; 3 columns LDS form,
+ * 4 columns direct form -- mi_interp1_cols_nearest_f64_dev; 0 for any other value of form. */
+size_t mi_debug_nearest_launches(int form);
 /* Test hook: which closed form of the abscissae a mode-0 table evaluates (0 fma(i, dx, x0); 1 x0 + i*dx;
  * 2 x0 + span*(i/(n-1)); 3 the same with the quotient from a Markstein step) and whether its last node is pinned to
  * xmax -- i.e. which instance of the interp1 kernels a call on this table launches.  Both are -1 for the {x,y} modes. */
@@ -195,6 +221,36 @@ mi_status mi_interp1_f64_host(mi_ctx* ctx, const mi_grid1* g, const double* xq, 
 mi_status mi_interp1_f64(mi_ctx* ctx, const double* x, const double* y, size_t n, const double* xq,
                          double* yq, size_t nq, double extrap_val);
 
+/* ---- 1-D interpolation, arma::interp1's "nearest" method ------------------
+ * yq[i] = Y[k], k the node the nearest rule at the top of this header picks for xq[i].  The calls take the SAME
+ * mi_grid1 handles as the linear calls: table construction, the four table modes, the closed forms and
+ * MI_GRID_SANITISE are untouched, and one table serves both methods.  A table of labels or states, a zero-order-hold
+ * resampling, a table with a NaN node (a linear lookup turns both neighbouring cells into NaN; nearest returns NaN only
+ * for the queries closest to that node).
+ * Each call copies the contract of the linear call it mirrors -- mi_interp1_f64_dev, mi_interp1_f64_host,
+ * mi_interp1_f64 (which sanitises X; "nearest"), in that order: argument checks and status codes, 8-B alignment,
+ * nq == 0 is MI_OK with nothing launched, 64-bit indexing, the device form asynchronous on the context's stream without
+ * allocation, copy or synchronisation (capturable).  Algorithmic HBM bytes per query: 8 (xq) + 8 (yq); a closed-form
+ * table (mode 0) is read with ONE 8-B gather per query, half the linear blend's table traffic.
+ * Kernel choice (csrc/mi_nearest1.hip; mi_debug_nearest_launches tells which) is by alignment, table size and
+ * mi_ctx_set_query_order only: MI_QUERIES_ORDERED -> the streaming kernel; MI_QUERIES_RANDOM or MI_QUERIES_AUTO -> the
+ * whole-table-in-LDS kernel where the linear dispatcher's window admits it (table <= 128 KiB, nq >= 2^20), else the
+ * streaming kernel; pointers that are not 16-B aligned -> the scalar kernel.  The nearest calls never read or write the
+ * context's order probe, so they never change which kernel a later linear call launches.
+ * Which call when: nearest-node lookup -> these calls.  There is NO region-sweep form of nearest: unordered queries over
+ * a table larger than L2 take the streaming kernel here, and may then be SLOWER than mi_interp1_f64_dev, whose region
+ * sweep orders such queries by table region; ordered or clustered queries, and tables that fit L2, stream as the linear
+ * call does. */
+mi_status mi_interp1_nearest_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
+                                     size_t nq, double extrap_val);
+/* host pointers, synchronous: the chunked, pinned path of mi_interp1_f64_host around the nearest kernels */
+mi_status mi_interp1_nearest_f64_host(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq,
+                                      size_t nq, double extrap_val);
+/* One-shot arma::interp1(X,Y,XI,YI,"nearest",extrap) equivalent on host pointers (sanitises X, builds a temporary
+ * table, synchronous). */
+mi_status mi_interp1_nearest_f64(mi_ctx* ctx, const double* x, const double* y, size_t n, const double* xq,
+                                 double* yq, size_t nq, double extrap_val);
+
 /* ---- 2-D tables and scattered bilinear interpolation ------------------
  * z is column-major ny x nx, i.e. arma::mat(ny, nx).memptr(): z[i + j*ny] =
  * Z(y_i, x_j).  Blend along y inside the two bracketing columns, then along
@@ -253,6 +309,19 @@ mi_status mi_interp1_cols_f64_dev(mi_ctx* ctx, const mi_axis1* axis, const doubl
                                   const double* xi_dev, size_t nxi, double* yi_dev, size_t ldyi, double extrap_val);
 mi_status mi_interp1_cols_f64_host(mi_ctx* ctx, const mi_axis1* axis, const double* y, size_t ldy, size_t ncols,
                                    const double* xi, size_t nxi, double* yi, size_t ldyi, double extrap_val);
+/* The "nearest" method over the columns of a matrix: mi_interp1_cols_f64_dev's contract word for word (layouts, argument
+ * checks and status codes, 8-B alignment, ncols == 0 or nxi == 0 is MI_OK with nothing launched, rows n..ldy-1 of y never
+ * read, rows nxi..ldyi-1 of yi never written, asynchronous on the context's stream) with the nearest rule in place of the
+ * blend:
+ *     yi[i + c*ldyi] == what mi_interp1_nearest_f64_dev returns for xi[i] on the table (x, y[:, c]),  bit for bit
+ * -- the stored value of the nearest node, inf / NaN / -0.0 as they are.  Each query is located once per call into one
+ * int32 (4 B per query in the context's record workspace -- the slot the linear call's 16-B records use, in stream order,
+ * grown on demand: linear and nearest calls back to back do not disturb each other); one kernel follows, which stages each
+ * column once in LDS for n <= 8192 and gathers y[k, c] through L2 for longer columns (mi_debug_nearest_launches: 3 / 4).
+ * There is no host-pointer, group or arma:: form of this call: like the host forms of the row calls they wait for the
+ * cause of the open fault on the strided host-copy path. */
+mi_status mi_interp1_cols_nearest_f64_dev(mi_ctx* ctx, const mi_axis1* axis, const double* y_dev, size_t ldy, size_t ncols,
+                                          const double* xi_dev, size_t nxi, double* yi_dev, size_t ldyi, double extrap_val);
 
 /* ---- interp1 over paired columns (an X per column of Y) -------------------
  * A batch of independent tables that all answer the same queries: column c of y is sampled at the nodes in column c of
