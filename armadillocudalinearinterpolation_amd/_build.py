@@ -19,7 +19,13 @@ HIPCC_FLAGS = [
 # mi_edm.hip without the SLP vectoriser: it pairs the firing test's independent fp32 operations into v_pk_*_f32, and on
 # gfx950 a packed fp32 instruction takes more issue time than the two it replaces (same bits either way; measured
 # 116.4 -> 113.6 ms at N = 1024, 45.2 -> 43.0 ms at N = 512, profiles/r04_edm_evolve_steps.log).
-PER_SOURCE_FLAGS = {"mi_edm.hip": ["-fno-slp-vectorize"]}
+# mi_interp1.hip exports its dispatcher and its launch counter under a second name: the names themselves are defined
+# in mi_sweep_phase.hip, which forwards to these (the files of the interp1 family stay as they are, byte for byte).
+PER_SOURCE_FLAGS = {
+    "mi_edm.hip": ["-fno-slp-vectorize"],
+    "mi_interp1.hip": ["-Dmi_interp1_f64_dev_v2=mi_interp1_f64_dev_v2_base",
+                       "-Dmi_debug_sweep_ds_launches=mi_debug_sweep_ds_launches_base"],
+}
 
 
 def sources():

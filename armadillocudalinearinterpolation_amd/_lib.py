@@ -49,6 +49,8 @@ SIGNATURES = {
     "mi_abi_version": (_i32, []),
     "mi_debug_pinned_ranges": (_sz, []),
     "mi_debug_sweep_ds_launches": (_sz, []),
+    "mi_debug_sweep_ds_launches_base": (_sz, []),
+    "mi_debug_interp1_phased_sweep": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl, _i32, _i32]),
     "mi_debug_each_launches": (_sz, [_i32]),
     "mi_debug_slices2_launches": (_sz, [_i32]),
     "mi_debug_rows1_launches": (_sz, [_i32]),
@@ -74,6 +76,7 @@ SIGNATURES = {
     "mi_grid1_info": (_i32, [_vp, C.POINTER(_sz), C.POINTER(_i32), C.POINTER(_sz)]),
     "mi_interp1_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
     "mi_interp1_f64_dev_v2": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
+    "mi_interp1_f64_dev_v2_base": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
     "mi_interp1_f64_host": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),
     "mi_interp1_f64": (_i32, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _dbl]),
     "mi_interp1_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl]),

@@ -84,7 +84,10 @@ extern "C" {
  *                mi_interp1_nearest_f64_dev, mi_interp1_nearest_f64_host, mi_interp1_nearest_f64,
  *                mi_interp1_cols_nearest_f64_dev, mi_debug_nearest_launches (arma::interp1's "nearest" method: table
  *                lookup on the mi_grid1 handles of the linear calls, and the columns of a matrix; device form only
- *                for the columns) */
+ *                for the columns);
+ *                mi_interp1_f64_dev_v2_base, mi_debug_sweep_ds_launches_base, mi_debug_interp1_phased_sweep (the region
+ *                sweep with the XCD groups out of phase, csrc/mi_sweep_phase.hip: the interp1 family's own dispatcher
+ *                and counter under a second name, and the phased kernel on its own for tests) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -122,6 +125,9 @@ int mi_abi_version(void);
 size_t mi_debug_pinned_ranges(void);
 /* Test hook: launches of the deferred-store region sweep (mi_interp1_f64_dev_v2) by this process so far. */
 size_t mi_debug_sweep_ds_launches(void);
+/* Test hook: the part of mi_debug_sweep_ds_launches that the interp1 family's own deferred-store kernel accounts for
+ * (csrc/mi_interp1.hip); the rest are launches of the phased kernel (csrc/mi_sweep_phase.hip). */
+size_t mi_debug_sweep_ds_launches_base(void);
 /* Test hook: calls of mi_interp1_each_f64_dev by this process so far that took the given form: 0 thin kernel, 1 LDS
  * form, 2 direct form, 3 forwarded to mi_interp1_pairs_f64_dev; 0 for any other value of form. */
 size_t mi_debug_each_launches(int form);
@@ -212,6 +218,20 @@ mi_status mi_interp1_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq_de
  * environment (read once per process) every call does. */
 mi_status mi_interp1_f64_dev_v2(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
                                 size_t nq, double extrap_val);
+/* mi_interp1_f64_dev_v2 is defined in csrc/mi_sweep_phase.hip: exactly where the dispatcher above would launch the
+ * deferred-store sweep of a closed-form table (mode 0) as the call's only kernel, it launches that kernel's restatement
+ * with the XCD groups out of phase (same results bit for bit); every other call, argument errors included, goes to
+ * mi_interp1_f64_dev_v2_base, which is csrc/mi_interp1.hip's dispatcher as it is.  MI_SWEEP_XCD_PHASES=P or P:period_ns
+ * in the environment (read once per process) sets the number of phase classes (1, 2, 4, 8) and the tile period the
+ * delays are cut from; P = 0, or any of the family's MI_SWEEP_* hooks present, forwards every call to the base. */
+mi_status mi_interp1_f64_dev_v2_base(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
+                                     size_t nq, double extrap_val);
+/* Test hook: the phased kernel on its own, whatever the size thresholds say, on at most max_workgroups workgroups (and
+ * at most one per CU), so that a few tiles per workgroup are reached with few queries.  Closed-form tables only; both
+ * pointers 16-byte aligned; phases 1, 2, 4 or 8; max_workgroups >= 1; else MI_ERR_INVALID_ARG.  Counted by
+ * mi_debug_sweep_ds_launches. */
+mi_status mi_debug_interp1_phased_sweep(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
+                                        size_t nq, double extrap_val, int phases, int max_workgroups);
 /* Host convenience used by the arma::vec wrapper: uploads xq, runs, downloads
  * (synchronous). */
 mi_status mi_interp1_f64_host(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq,
