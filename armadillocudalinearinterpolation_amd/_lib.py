@@ -56,6 +56,7 @@ SIGNATURES = {
     "mi_debug_rows1_launches": (_sz, [_i32]),
     "mi_debug_rowpairs_launches": (_sz, [_i32]),
     "mi_debug_nearest_launches": (_sz, [_i32]),
+    "mi_debug_nearest_batched_launches": (_sz, [_i32]),
     "mi_debug_grid1_formula": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "mi_last_error": (C.c_char_p, [_vp]),
     "mi_ctx_create": (_i32, [_i32, _pp]),
@@ -98,10 +99,12 @@ SIGNATURES = {
     "mi_interp1_cols_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
     "mi_interp1_pairs_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp1_pairs_f64_host": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _dbl, _vp]),
+    "mi_interp1_pairs_nearest_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp1_each_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp1_each_f64_host": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp2_slices_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl]),
     "mi_interp1_rows_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
+    "mi_interp1_rows_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
     "mi_interp1_rowpairs_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _dbl, _vp]),
     "mi_restrict_f32_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _vp, _sz]),
     "mi_restrict_f32_host": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _vp, _sz]),

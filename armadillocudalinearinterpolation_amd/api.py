@@ -464,7 +464,9 @@ class Axis1(_Handle):
     Data stored the other way round -- one table per ROW of a column-major (m, n) matrix, i.e. a C-contiguous (n, m)
     "time-major" buffer viewed .T, every time level a contiguous block -- goes through interp_rows, and a cube of fields
     at n time levels through interp_stack (interpolation along the slice index); both are one call of
-    mi_interp1_rows_f64_dev and bit-identical to interp_cols on the transposed data.  Device tensors only."""
+    mi_interp1_rows_f64_dev and bit-identical to interp_cols on the transposed data.  Device tensors only.
+    interp_cols_nearest, interp_rows_nearest and interp_stack_nearest are the same calls with arma::interp1's "nearest"
+    method: the stored value of the nearest node, copied."""
 
     _destroy = "mi_axis1_destroy"
 
@@ -562,13 +564,23 @@ class Axis1(_Handle):
         order; out: (m, nxi) tensor in the same layout (default: the .T view of a new contiguous (nxi, m) buffer).
         Returns out with out[r, i] = interp1 of xi[i] on (X, Y[r, :]), bit-identical to interp_cols on the transposed
         data; asynchronous on the context's stream."""
+        return Axis1._rows_call(self, "mi_interp1_rows_f64_dev", Y, xi, out, extrap)
+
+    def interp_rows_nearest(self, Y, xi, out=None, extrap=math.nan):
+        """interp_rows with arma::interp1's "nearest" method (mi_interp1_rows_nearest_f64_dev): out[r, i] = Y[r, k], k the
+        node nearest to xi[i] (a tie keeps the left node; the stored value comes back as it is), bit-identical to
+        interp_cols_nearest on the transposed data.  Arguments and layouts as interp_rows."""
+        return Axis1._rows_call(self, "mi_interp1_rows_nearest_f64_dev", Y, xi, out, extrap)
+
+    def _rows_call(self, fn, Y, xi, out, extrap):
+        """the argument rules of interp_rows, written once for both methods; fn names the C function"""
         ldy, m = self._rows_view(Y, self.n, "Y")
         _need_f64_cuda(xi, "xi", True)
         _need_f64_cuda(Y, "Y", False)
         nxi = xi.numel()
         out, ldyi = _out_rows(out, m, nxi, Y)
-        check(self._L.mi_interp1_rows_f64_dev(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, m, _ptr(xi), nxi,
-                                              C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
+        check(getattr(self._L, fn)(self._ctx._h, self._h, C.c_void_p(Y.data_ptr()), ldy, m, _ptr(xi), nxi,
+                                   C.c_void_p(out.data_ptr()), ldyi, float(extrap)), self._ctx._h)
         return out
 
     def interp_stack(self, Z, ti, out=None, extrap=math.nan):
@@ -577,6 +589,16 @@ class Axis1(_Handle):
         stride may exceed ny*nx); ti: contiguous float64 CUDA tensor of nti times in any order; out: (ny, nx, nti) tensor
         of the same layout (default: the .permute(2, 1, 0) view of a new contiguous (nti, nx, ny) buffer).  Returns out
         with out[i, j, k] = interp1 of ti[k] on (X, Z[i, j, :]): one call of mi_interp1_rows_f64_dev with m = ny*nx."""
+        return Axis1._stack_call(self, "mi_interp1_rows_f64_dev", Z, ti, out, extrap)
+
+    def interp_stack_nearest(self, Z, ti, out=None, extrap=math.nan):
+        """interp_stack with the "nearest" method: out[i, j, k] = Z[i, j, s], s the slice whose node is nearest to ti[k]
+        -- the snapshot closest in time, a zero-order hold across the slices (a tie keeps the earlier slice).  One call of
+        mi_interp1_rows_nearest_f64_dev with m = ny*nx; arguments and layouts as interp_stack."""
+        return Axis1._stack_call(self, "mi_interp1_rows_nearest_f64_dev", Z, ti, out, extrap)
+
+    def _stack_call(self, fn, Z, ti, out, extrap):
+        """the argument rules of interp_stack, written once for both methods; fn names the C function"""
         ny, nx, zstride, S = self._stack_view(Z, "Z")
         if S != self.n:
             raise ValueError("Z must hold one slice per node of the axis (%d), not %d" % (self.n, S))
@@ -587,8 +609,8 @@ class Axis1(_Handle):
         oy, ox, ostride, So = self._stack_view(out, "out")
         if (oy, ox, So) != (ny, nx, nti):
             raise ValueError("out must have shape (%d, %d, %d)" % (ny, nx, nti))
-        check(self._L.mi_interp1_rows_f64_dev(self._ctx._h, self._h, C.c_void_p(Z.data_ptr()), zstride, ny * nx, _ptr(ti), nti,
-                                              C.c_void_p(out.data_ptr()), ostride, float(extrap)), self._ctx._h)
+        check(getattr(self._L, fn)(self._ctx._h, self._h, C.c_void_p(Z.data_ptr()), zstride, ny * nx, _ptr(ti), nti,
+                                   C.c_void_p(out.data_ptr()), ostride, float(extrap)), self._ctx._h)
         return out
 
     def interp_cols_host(self, Y, xi, extrap=math.nan):
@@ -654,12 +676,25 @@ def interp_pairs(ctx, X, Y, xi, lens=None, out=None, extrap=math.nan, want_ok=Fa
     buffer).  X is validated on the device at every call: a column whose length is outside [2, n] or whose nodes are not
     finite and strictly increasing gives NaN in all its outputs.  Returns the (nxi, B) result, or (result, ok) with
     want_ok=True, ok a (B,) int32 CUDA tensor (1 good, 0 bad).  Asynchronous on the context's stream."""
+    return _pairs_call("mi_interp1_pairs_f64_dev", ctx, X, Y, xi, lens, out, extrap, want_ok)
+
+
+def interp_pairs_nearest(ctx, X, Y, xi, lens=None, out=None, extrap=math.nan, want_ok=False):
+    """interp_pairs with arma::interp1's "nearest" method (mi_interp1_pairs_nearest_f64_dev): out[i, c] = Y[k, c], k the
+    node of column c of X nearest to xi[i] (a tie keeps the left node; the stored value comes back as it is) -- the state
+    at the event closest to each mesh time.  Arguments, layouts, the bad-column rule and the return value as
+    interp_pairs."""
+    return _pairs_call("mi_interp1_pairs_nearest_f64_dev", ctx, X, Y, xi, lens, out, extrap, want_ok)
+
+
+def _pairs_call(fn, ctx, X, Y, xi, lens, out, extrap, want_ok):
+    """the argument rules of interp_pairs, written once for both methods; fn names the C function"""
     _need_f64_cuda(xi, "xi", True)
     n, B, ldx, ldy, nxi, _, out, ldyi, ok = _paired_args(X, Y, lambda B: (xi.numel(), 0), lens, out, want_ok)
-    check(ctx._L.mi_interp1_pairs_f64_dev(ctx._h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, n,
-                                          C.c_void_p(lens.data_ptr()) if lens is not None else None, B, _ptr(xi), nxi,
-                                          C.c_void_p(out.data_ptr()), ldyi, float(extrap),
-                                          C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
+    check(getattr(ctx._L, fn)(ctx._h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, n,
+                              C.c_void_p(lens.data_ptr()) if lens is not None else None, B, _ptr(xi), nxi,
+                              C.c_void_p(out.data_ptr()), ldyi, float(extrap),
+                              C.c_void_p(ok.data_ptr()) if want_ok else None), ctx._h)
     return (out, ok) if want_ok else out
 
 

@@ -85,6 +85,9 @@ extern "C" {
  *                mi_interp1_cols_nearest_f64_dev, mi_debug_nearest_launches (arma::interp1's "nearest" method: table
  *                lookup on the mi_grid1 handles of the linear calls, and the columns of a matrix; device form only
  *                for the columns);
+ *                mi_interp1_rows_nearest_f64_dev, mi_interp1_pairs_nearest_f64_dev, mi_debug_nearest_batched_launches
+ *                (the "nearest" method along the rows of a matrix / across the slices of a cube, and over paired
+ *                columns; device form only);
  *                mi_interp1_f64_dev_v2_base, mi_debug_sweep_ds_launches_base, mi_debug_interp1_phased_sweep (the region
  *                sweep with the XCD groups out of phase, csrc/mi_sweep_phase.hip: the interp1 family's own dispatcher
  *                and counter under a second name, and the phased kernel on its own for tests) */
@@ -145,6 +148,10 @@ size_t mi_debug_rowpairs_launches(int form);
  * 1 whole table in LDS, 2 scalar kernel (pointers not 16-B aligned) -- mi_interp1_nearest_f64_dev; 3 columns LDS form,
  * 4 columns direct form -- mi_interp1_cols_nearest_f64_dev; 0 for any other value of form. */
 size_t mi_debug_nearest_launches(int form);
+/* Test hook: calls of the batched nearest entry points by this process so far that took the given form: 0 rows tile body
+ * with 16-B accesses, 1 rows tile body with 8-B accesses, 2 rows flat body (m < 256) -- mi_interp1_rows_nearest_f64_dev;
+ * 3 pairs LDS form (n <= 4096), 4 pairs direct form -- mi_interp1_pairs_nearest_f64_dev; 0 for any other value of form. */
+size_t mi_debug_nearest_batched_launches(int form);
 /* Test hook: which closed form of the abscissae a mode-0 table evaluates (0 fma(i, dx, x0); 1 x0 + i*dx;
  * 2 x0 + span*(i/(n-1)); 3 the same with the quotient from a Markstein step) and whether its last node is pinned to
  * xmax -- i.e. which instance of the interp1 kernels a call on this table launches.  Both are -1 for the {x,y} modes. */
@@ -260,7 +267,9 @@ mi_status mi_interp1_f64(mi_ctx* ctx, const double* x, const double* y, size_t n
  * Which call when: nearest-node lookup -> these calls.  There is NO region-sweep form of nearest: unordered queries over
  * a table larger than L2 take the streaming kernel here, and may then be SLOWER than mi_interp1_f64_dev, whose region
  * sweep orders such queries by table region; ordered or clustered queries, and tables that fit L2, stream as the linear
- * call does. */
+ * call does.  Many tables at once: one X, a table per column -> mi_interp1_cols_nearest_f64_dev; one X, a table per ROW
+ * or the slices of a cube -> mi_interp1_rows_nearest_f64_dev; an X per column -> mi_interp1_pairs_nearest_f64_dev.
+ * There is no nearest form of the each, rowpairs and slices calls. */
 mi_status mi_interp1_nearest_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
                                      size_t nq, double extrap_val);
 /* host pointers, synchronous: the chunked, pinned path of mi_interp1_f64_host around the nearest kernels */
@@ -373,13 +382,32 @@ mi_status mi_interp1_cols_nearest_f64_dev(mi_ctx* ctx, const mi_axis1* axis, con
  * NULL, MI_OK when col_ok was given.
  * Which call when: one X for every column -> mi_interp1_cols_f64_dev (it locates each query once per call); an X per
  * column -> this call; one column with many queries -> mi_grid1 and mi_interp1_f64_dev; the same data stored the other
- * way round, an X per ROW -> mi_interp1_rowpairs_f64_dev, without a transpose. */
+ * way round, an X per ROW -> mi_interp1_rowpairs_f64_dev, without a transpose; the node closest to each query in
+ * place of the blend (labels, states, values that must not be averaged) -> mi_interp1_pairs_nearest_f64_dev, also for
+ * very short columns: it has no thin form, and the Restrict shape n = 2 goes through its LDS form. */
 mi_status mi_interp1_pairs_f64_dev(mi_ctx* ctx, const double* x_dev, size_t ldx, const double* y_dev, size_t ldy, size_t n,
                                    const uint32_t* len_dev, size_t ncols, const double* xi_dev, size_t nxi,
                                    double* yi_dev, size_t ldyi, double extrap_val, uint32_t* col_ok_dev);
 mi_status mi_interp1_pairs_f64_host(mi_ctx* ctx, const double* x, size_t ldx, const double* y, size_t ldy, size_t n,
                                     const uint32_t* len, size_t ncols, const double* xi, size_t nxi, double* yi,
                                     size_t ldyi, double extrap_val, uint32_t* col_ok);
+/* The "nearest" method over paired columns: mi_interp1_pairs_f64_dev's contract word for word (layouts, len and n_c, the
+ * BAD-column rule -- all nxi outputs of a bad column are NaN -- col_ok, argument checks and status codes with this
+ * function's name in the text, alignment, ncols == 0 or nxi == 0 is MI_OK with nothing launched or written, rows behind
+ * n_c never reach a result, asynchronous on the context's stream) with the nearest rule in place of the blend:
+ *     yi[i + c*ldyi] == what mi_interp1_nearest_f64_dev returns for xi[i] on the table (x[0:n_c, c], y[0:n_c, c]) built
+ *                       without MI_GRID_SANITISE,  bit for bit
+ * -- the stored value of the nearest node, inf / NaN / -0.0 as they are; a tie keeps the left node.  The state at the
+ * event closest to each mesh time: labels, spike indices stored as doubles, any column whose values must not be averaged.
+ * Allocation: none for n <= 4096 (columns are staged and validated in LDS; after the bracket search an output costs two
+ * subtractions, a compare and one LDS read); for longer columns the validation flags go into col_ok_dev when given, else
+ * into the context's record workspace (4 B per column), and y[k, c] is gathered once through L2
+ * (csrc/mi_nearest_batched.hip; mi_debug_nearest_batched_launches: 3 / 4).  There is no thin form for very short columns:
+ * n = 2 goes through the LDS form.  There is no host-pointer, group or arma:: form of this call. */
+mi_status mi_interp1_pairs_nearest_f64_dev(mi_ctx* ctx, const double* x_dev, size_t ldx, const double* y_dev, size_t ldy,
+                                           size_t n, const uint32_t* len_dev, size_t ncols, const double* xi_dev,
+                                           size_t nxi, double* yi_dev, size_t ldyi, double extrap_val,
+                                           uint32_t* col_ok_dev);
 
 /* ---- interp1 over paired columns, a query vector per column ---------------
  * mi_interp1_pairs_f64_dev with an XI per column: an ensemble of independent tables, each with its own X, Y and XI.
@@ -466,9 +494,29 @@ mi_status mi_interp2_slices_f64_dev(mi_ctx* ctx, const mi_axis1* ax, const mi_ax
  * There is no host-pointer, group or arma:: form of this call.
  * Which call when: one table per ROW, or interpolation across the slices of a cube -> this call; one table per column ->
  * mi_interp1_cols_f64_dev; a single row with many queries (m == 1) -> mi_grid1 and mi_interp1_f64_dev; one table per row
- * AND an X per row -> mi_interp1_rowpairs_f64_dev. */
+ * AND an X per row -> mi_interp1_rowpairs_f64_dev; the snapshot closest in time (a zero-order hold across the slices of
+ * a cube) in place of the blend -> mi_interp1_rows_nearest_f64_dev. */
 mi_status mi_interp1_rows_f64_dev(mi_ctx* ctx, const mi_axis1* axis, const double* y_dev, size_t ldy, size_t m,
                                   const double* xi_dev, size_t nxi, double* yi_dev, size_t ldyi, double extrap_val);
+/* The "nearest" method along the rows of a matrix / across the slices of a cube: mi_interp1_rows_f64_dev's contract word
+ * for word (layouts, argument checks and status codes with this function's name in the text, 8-B alignment, m == 0 or
+ * nxi == 0 is MI_OK with nothing launched or written, rows m..ldy-1 of y never read, rows m..ldyi-1 of yi never written,
+ * the axis-device check, asynchronous on the context's stream) with the nearest rule in place of the blend:
+ *     yi[r + i*ldyi] == what mi_interp1_nearest_f64_dev returns for xi[i] on the table (x, Y(r, :)),  bit for bit
+ * -- the stored value of the nearest node, inf / NaN / -0.0 as they are, and bit-identical to
+ * mi_interp1_cols_nearest_f64_dev on the transposed data.  A NaN or inf snapshot reaches the queries of its own two
+ * half-cells only, where the linear call loses both neighbouring cells.  Each query is located once per call into one
+ * int32 (nxi x 4 B in the context's record workspace, the slot of the linear calls' records, in stream order with them:
+ * linear and nearest calls back to back do not disturb each other); one kernel follows, in which an output column is a
+ * copy of ONE input column: a workgroup keeps one column of its 1024 rows in registers, so that with sorted xi every
+ * column of y some query is nearest to is read once and the others never, and with xi in no order ONE column is read per
+ * output (the linear call: two); for m < 256 a flat kernel gathers one value per output (csrc/mi_nearest_batched.hip;
+ * mi_debug_nearest_batched_launches: 0 / 1 / 2).  Algorithmic bytes: 8*m*(columns touched) + 8*m*nxi + 8*nxi.
+ * MI_ERR_INVALID_ARG also for sizes whose byte counts overflow (ldy*n, ldyi*nxi, nxi*4).
+ * There is no host-pointer, group or arma:: form of this call. */
+mi_status mi_interp1_rows_nearest_f64_dev(mi_ctx* ctx, const mi_axis1* axis, const double* y_dev, size_t ldy, size_t m,
+                                          const double* xi_dev, size_t nxi, double* yi_dev, size_t ldyi,
+                                          double extrap_val);
 
 /* ---- interp1 over paired rows (an X per row of Y) ---------------------------
  * mi_interp1_pairs_f64_dev for data stored the other way round: row r of y is sampled at the nodes in row r of x.  An
