@@ -51,6 +51,8 @@ SIGNATURES = {
     "mi_debug_sweep_ds_launches": (_sz, []),
     "mi_debug_sweep_ds_launches_base": (_sz, []),
     "mi_debug_interp1_phased_sweep": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl, _i32, _i32]),
+    "mi_debug_interp1_phased_sweep_ex": (_i32, [_vp, _vp, _vp, _vp, _sz, _dbl, _i32, _i32, _u32, _vp, _u32]),
+    "mi_debug_sweep_partition": (_i32, [_sz, _u32, _i32, _u32, _u32] + [C.POINTER(_u32)] * 3 + [C.POINTER(_sz)] * 6),
     "mi_debug_each_launches": (_sz, [_i32]),
     "mi_debug_slices2_launches": (_sz, [_i32]),
     "mi_debug_rows1_launches": (_sz, [_i32]),

@@ -90,7 +90,10 @@ extern "C" {
  *                columns; device form only);
  *                mi_interp1_f64_dev_v2_base, mi_debug_sweep_ds_launches_base, mi_debug_interp1_phased_sweep (the region
  *                sweep with the XCD groups out of phase, csrc/mi_sweep_phase.hip: the interp1 family's own dispatcher
- *                and counter under a second name, and the phased kernel on its own for tests) */
+ *                and counter under a second name, and the phased kernel on its own for tests);
+ *                mi_debug_interp1_phased_sweep_ex, mi_debug_sweep_partition (the phase classes set apart by work
+ *                instead of a clock wait: the kernel on its own with a first-tile table and optional clock stamps,
+ *                and the ownership function, csrc/mi_sweep_partition.hpp, on the host) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -228,9 +231,12 @@ mi_status mi_interp1_f64_dev_v2(mi_ctx* ctx, const mi_grid1* g, const double* xq
 /* mi_interp1_f64_dev_v2 is defined in csrc/mi_sweep_phase.hip: exactly where the dispatcher above would launch the
  * deferred-store sweep of a closed-form table (mode 0) as the call's only kernel, it launches that kernel's restatement
  * with the XCD groups out of phase (same results bit for bit); every other call, argument errors included, goes to
- * mi_interp1_f64_dev_v2_base, which is csrc/mi_interp1.hip's dispatcher as it is.  MI_SWEEP_XCD_PHASES=P or P:period_ns
- * in the environment (read once per process) sets the number of phase classes (1, 2, 4, 8) and the tile period the
- * delays are cut from; P = 0, or any of the family's MI_SWEEP_* hooks present, forwards every call to the base. */
+ * mi_interp1_f64_dev_v2_base, which is csrc/mi_interp1.hip's dispatcher as it is.
+ * MI_SWEEP_XCD_PHASES=P[:period_ns[:units]] in the environment (read once per process) sets the number of phase classes
+ * (1, 2, 4, 8), the tile period the clock delays are cut from, and the first-tile table of the shift by work, a digit
+ * 1..4 per class ("4:0:4123"; P = 1, 2, 4 only).  Without a units field, period_ns > 0 asks for the clock form and
+ * anything else runs the form shipped for P.  P = 0, or any of the family's MI_SWEEP_* hooks present, forwards every
+ * call to the base. */
 mi_status mi_interp1_f64_dev_v2_base(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
                                      size_t nq, double extrap_val);
 /* Test hook: the phased kernel on its own, whatever the size thresholds say, on at most max_workgroups workgroups (and
@@ -239,6 +245,27 @@ mi_status mi_interp1_f64_dev_v2_base(mi_ctx* ctx, const mi_grid1* g, const doubl
  * mi_debug_sweep_ds_launches. */
 mi_status mi_debug_interp1_phased_sweep(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
                                         size_t nq, double extrap_val, int phases, int max_workgroups);
+/* The same hook with the form of the phase shift chosen by the caller.  mi_debug_interp1_phased_sweep always runs the
+ * clock form (class c waits c/phases of a tile period before its first load, whole tiles of 16384 queries).
+ * first_units != 0 runs the shift by work instead: a decimal digit 1..4 per class, class 0 first (4123 = {4, 1, 2, 3}),
+ * the number of 4096-query units in the first tile of a workgroup of that class; phases must be 1, 2 or 4 then and
+ * nobody waits.  first_units == 0 is the clock form.  stamps_dev: NULL, or device memory for max_workgroups * stamp_cap
+ * values (stamp_cap >= 2): workgroup b writes the wall clock to stamps_dev[b * stamp_cap + slot] at entry (slot 0), at
+ * the start of the gather step of its tile i (slot 1 + i) and at exit (slot 1 + its tile count); slots beyond stamp_cap
+ * are dropped, slots nobody writes keep their contents.  Results are the same bytes in every form. */
+mi_status mi_debug_interp1_phased_sweep_ex(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
+                                           size_t nq, double extrap_val, int phases, int max_workgroups,
+                                           unsigned first_units, unsigned long long* stamps_dev, unsigned stamp_cap);
+/* Which queries the workgroup of a rank owns under the shift by work (csrc/mi_sweep_partition.hpp, the function the
+ * kernel itself calls; no device is touched).  All starts are in units of 4096 queries.  Tile i of the workgroup starts
+ * at  i == 0 ? first_start : i == ntiles-1 ? last_start : i == ntiles-2 ? pen_start : mid_origin + (i-1) mid_step  and
+ * has  i == 0 ? first_tile_units : i == ntiles-1 ? last_tile_units : 4  units; work is the sum.  The nq % 4096 queries
+ * behind the last unit belong to rank nwg - 1.  Any out pointer may be NULL.  MI_ERR_INVALID_ARG unless phases is 1, 2
+ * or 4, first_units has that many digits 1..4 and rank < nwg. */
+mi_status mi_debug_sweep_partition(size_t nq, unsigned nwg, int phases, unsigned first_units, unsigned rank,
+                                   unsigned* ntiles, unsigned* first_tile_units, unsigned* last_tile_units, size_t* work,
+                                   size_t* first_start, size_t* mid_origin, size_t* mid_step, size_t* pen_start,
+                                   size_t* last_start);
 /* Host convenience used by the arma::vec wrapper: uploads xq, runs, downloads
  * (synchronous). */
 mi_status mi_interp1_f64_host(mi_ctx* ctx, const mi_grid1* g, const double* xq, double* yq,
