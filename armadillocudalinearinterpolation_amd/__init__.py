@@ -7,6 +7,6 @@ Importing this package does not touch the GPU; the first Context() does.
 from ._lib import MiError, lib_path, load  # noqa: F401
 from .api import (  # noqa: F401
     MATH_EXACT, MATH_FAST, Axis1, Context, EventDrivenMap, Grid1, Grid2, Group, Timer, default_edm_params, interp1,
-    interp1_nearest, interp2_slices, interp_each, interp_each_host, interp_pairs, interp_pairs_host, interp_pairs_nearest,
-    interp_rowpairs, masked_mean, restrict, restrict_mean, shard_bounds,
+    interp1_nearest, interp2_slices, interp2_slices_nearest, interp_each, interp_each_host, interp_pairs, interp_pairs_host,
+    interp_pairs_nearest, interp_rowpairs, masked_mean, restrict, restrict_mean, shard_bounds,
 )

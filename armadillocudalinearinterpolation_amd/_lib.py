@@ -59,6 +59,7 @@ SIGNATURES = {
     "mi_debug_rowpairs_launches": (_sz, [_i32]),
     "mi_debug_nearest_launches": (_sz, [_i32]),
     "mi_debug_nearest_batched_launches": (_sz, [_i32]),
+    "mi_debug_nearest2_launches": (_sz, [_i32]),
     "mi_debug_grid1_formula": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "mi_last_error": (C.c_char_p, [_vp]),
     "mi_ctx_create": (_i32, [_i32, _pp]),
@@ -93,6 +94,9 @@ SIGNATURES = {
     "mi_interp2_f64_host": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _dbl]),
     "mi_interp2_grid_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _dbl]),
     "mi_interp2_grid_f64_host": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _dbl]),
+    "mi_interp2_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _sz, _dbl]),
+    "mi_interp2_grid_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _dbl]),
+    "mi_interp2_grid_nearest_f64_host": (_i32, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _dbl]),
     "mi_axis1_create": (_i32, [_vp, _vp, _sz, C.c_uint, _pp]),
     "mi_axis1_create_uniform": (_i32, [_vp, _dbl, _dbl, _sz, _pp]),
     "mi_axis1_destroy": (_i32, [_vp]),
@@ -105,6 +109,7 @@ SIGNATURES = {
     "mi_interp1_each_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp1_each_f64_host": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _dbl, _vp]),
     "mi_interp2_slices_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl]),
+    "mi_interp2_slices_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl]),
     "mi_interp1_rows_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
     "mi_interp1_rows_nearest_f64_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _dbl]),
     "mi_interp1_rowpairs_f64_dev": (_i32, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _dbl, _vp]),

@@ -395,6 +395,15 @@ class Grid2:
         return {"table_bytes": tb.value}
 
     def interp(self, xq, yq, out=None, extrap=math.nan):
+        return self._scattered_call("mi_interp2_f64_dev", xq, yq, out, extrap)
+
+    def interp_nearest(self, xq, yq, out=None, extrap=math.nan):
+        """arma::interp2's "nearest" method on scattered pairs (mi_interp2_nearest_f64_dev): interp's arguments and
+        layouts; out[i] = Z(ky, kx), the stored value of the node the nearest rule picks on each axis (a tie keeps the
+        left node), inf / NaN / -0.0 as they are."""
+        return self._scattered_call("mi_interp2_nearest_f64_dev", xq, yq, out, extrap)
+
+    def _scattered_call(self, fn, xq, yq, out, extrap):
         torch = _torch()
         for t in (xq, yq):
             if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
@@ -405,8 +414,8 @@ class Grid2:
             out = torch.empty_like(xq)
         elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == xq.numel()):
             raise ValueError("out must be a contiguous float64 CUDA tensor of the same size")     # Grid1.interp's rule
-        check(self._L.mi_interp2_f64_dev(self._ctx._h, self._h, _ptr(xq), _ptr(yq), _ptr(out), xq.numel(),
-                                         float(extrap)), self._ctx._h)
+        check(getattr(self._L, fn)(self._ctx._h, self._h, _ptr(xq), _ptr(yq), _ptr(out), xq.numel(),
+                                   float(extrap)), self._ctx._h)
         return out
 
     def interp_host(self, xq, yq, extrap=math.nan):
@@ -420,6 +429,14 @@ class Grid2:
         """arma::interp2's gridded output: ZI[i, j] = Z at (xi[j], yi[i]), a (nyi, nxi) tensor stored column-major (the
         .T view of a contiguous (nxi, nyi) buffer).  xi, yi: contiguous float64 CUDA tensors (any order); out: that
         contiguous (nxi, nyi) float64 buffer.  Asynchronous on the context's stream."""
+        return self._grid_call("mi_interp2_grid_f64_dev", xi, yi, out, extrap)
+
+    def interp_grid_nearest(self, xi, yi, out=None, extrap=math.nan):
+        """arma::interp2's "nearest" method, gridded output (mi_interp2_grid_nearest_f64_dev): interp_grid's arguments
+        and layouts; ZI[i, j] = Z(ky(yi[i]), kx(xi[j])), bit-identical to interp_nearest on that pair."""
+        return self._grid_call("mi_interp2_grid_nearest_f64_dev", xi, yi, out, extrap)
+
+    def _grid_call(self, fn, xi, yi, out, extrap):
         torch = _torch()
         for t in (xi, yi):
             if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
@@ -429,16 +446,23 @@ class Grid2:
             out = torch.empty((nxi, nyi), dtype=torch.float64, device=xi.device)
         elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (nxi, nyi)):
             raise ValueError("out must be a contiguous float64 CUDA tensor of shape (len(xi), len(yi))")
-        check(self._L.mi_interp2_grid_f64_dev(self._ctx._h, self._h, _ptr(xi), nxi, _ptr(yi), nyi, _ptr(out),
-                                              float(extrap)), self._ctx._h)
+        check(getattr(self._L, fn)(self._ctx._h, self._h, _ptr(xi), nxi, _ptr(yi), nyi, _ptr(out),
+                                   float(extrap)), self._ctx._h)
         return out.T
 
     def interp_grid_host(self, xi, yi, extrap=math.nan):
         """host form of interp_grid: numpy axes in, a Fortran-ordered (nyi, nxi) array out (synchronous)"""
+        return self._grid_host_call("mi_interp2_grid_f64_host", xi, yi, extrap)
+
+    def interp_grid_nearest_host(self, xi, yi, extrap=math.nan):
+        """host form of interp_grid_nearest: numpy axes in, a Fortran-ordered (nyi, nxi) array out (synchronous)"""
+        return self._grid_host_call("mi_interp2_grid_nearest_f64_host", xi, yi, extrap)
+
+    def _grid_host_call(self, fn, xi, yi, extrap):
         xi, yi = _np64(xi), _np64(yi)
         out = np.empty((xi.size, yi.size))
-        check(self._L.mi_interp2_grid_f64_host(self._ctx._h, self._h, _ptr(xi), xi.size, _ptr(yi), yi.size, _ptr(out),
-                                               float(extrap)), self._ctx._h)
+        check(getattr(self._L, fn)(self._ctx._h, self._h, _ptr(xi), xi.size, _ptr(yi), yi.size, _ptr(out),
+                                   float(extrap)), self._ctx._h)
         return out.T
 
     def close(self):
@@ -831,6 +855,18 @@ def interp2_slices(ctx, ax, ay, Z, xi, yi, out=None, extrap=math.nan):
     out: (nyi, nxi, S) tensor of the same layout (default: the .permute(2, 1, 0) view of a new contiguous (S, nxi, nyi)
     buffer).  Returns out with out[i, j, s] = Z[:, :, s] at (xi[j], yi[i]), bit-identical to Grid2.interp_grid on that
     slice; asynchronous on the context's stream."""
+    return _slices_call("mi_interp2_slices_f64_dev", ctx, ax, ay, Z, xi, yi, out, extrap)
+
+
+def interp2_slices_nearest(ctx, ax, ay, Z, xi, yi, out=None, extrap=math.nan):
+    """mi_interp2_slices_nearest_f64_dev: arma::interp2's "nearest" method for every slice of a cube, Z read where it
+    lies.  interp2_slices' arguments, layouts and default output; out[i, j, s] = Z[ky(yi[i]), kx(xi[j]), s], the stored
+    value (inf / NaN / -0.0 as they are), bit-identical to Grid2.interp_grid_nearest on that slice; asynchronous on the
+    context's stream."""
+    return _slices_call("mi_interp2_slices_nearest_f64_dev", ctx, ax, ay, Z, xi, yi, out, extrap)
+
+
+def _slices_call(fn, ctx, ax, ay, Z, xi, yi, out, extrap):
     for t in (xi, yi):
         _need_f64_cuda(t, "query axes", True, "query axes must be contiguous float64 CUDA tensors")
     _need_f64_cuda(Z, "Z", False)
@@ -840,8 +876,8 @@ def interp2_slices(ctx, ax, ay, Z, xi, yi, out=None, extrap=math.nan):
     ldzi, zistride, So = _cube_view(out, nyi, nxi, "out")
     if So != S:
         raise ValueError("out must have as many slices as Z")
-    check(ctx._L.mi_interp2_slices_f64_dev(ctx._h, ax._h, ay._h, C.c_void_p(Z.data_ptr()), ldz, zstride, S, _ptr(xi), nxi,
-                                           _ptr(yi), nyi, C.c_void_p(out.data_ptr()), ldzi, zistride, float(extrap)), ctx._h)
+    check(getattr(ctx._L, fn)(ctx._h, ax._h, ay._h, C.c_void_p(Z.data_ptr()), ldz, zstride, S, _ptr(xi), nxi,
+                              _ptr(yi), nyi, C.c_void_p(out.data_ptr()), ldzi, zistride, float(extrap)), ctx._h)
     return out
 
 

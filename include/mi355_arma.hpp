@@ -21,6 +21,9 @@
 //   mi355::interp2(X, Y, Z, XI, YI, ZI)     ZI an arma::mat: == arma::interp2(X, Y, Z, XI, YI, ZI, "linear", extrap),
 //                                           ZI = YI.n_elem x XI.n_elem; Z = arma::mat(Y.n_elem, X.n_elem)
 //                                           ZI an arma::vec: scattered extension, one result per (XI[k], YI[k]) pair
+//   mi355::interp2(X, Y, Z, XI, YI, ZI, method)   ZI an arma::mat: == arma::interp2(..., method, extrap): "linear" or
+//                                           "nearest" (ZI(i, j) = Z(ky, kx), the stored value of the nearest node on each
+//                                           axis, a tie keeps the left node); any other string throws
 //   mi355::restrict_to_horizon(...)         RestrictKernel (EventDrivenMap.cu:769-785) on host vectors
 //   mi355::DeviceGroup grp(8); mi355::GroupInterp1Table tab(grp, X, Y); tab(XI, YI)
 //                                           the same call with the queries sharded over the GPUs of the node
@@ -264,6 +267,46 @@ inline void interp2(const arma::vec& X, const arma::vec& Y, const arma::mat& Z, 
                                             extrap_val);
     mi_grid2_destroy(g);
     check(st, dev.get(), "mi_interp2_grid_f64_host");
+}
+
+// arma::interp2(X, Y, Z, XI, YI, ZI, method, extrap_val) with Armadillo's two method strings (interp2 has no starred forms):
+//   "linear"    the overload above                                                (mi_interp2_grid_f64_host)
+//   "nearest"   ZI(i, j) = Z(ky, kx), the stored value of the node the nearest rule picks on each axis: a tie keeps the
+//               left node, inf / NaN / -0.0 come back as they are             (mi_interp2_grid_nearest_f64_host)
+// anything else throws std::invalid_argument, as Armadillo does.  XI and YI may be in any order.
+inline void interp2(const arma::vec& X, const arma::vec& Y, const arma::mat& Z, const arma::vec& XI,
+                    const arma::vec& YI, arma::mat& ZI, const char* method,
+                    double extrap_val = std::numeric_limits<double>::quiet_NaN(), Device& dev = Device::instance())
+{
+    const std::string m = method ? method : "";
+    if (m == "linear") return interp2(X, Y, Z, XI, YI, ZI, extrap_val, dev);
+    if (m != "nearest") throw std::invalid_argument("interp2(): unsupported interpolation type");
+    if (Z.n_rows != Y.n_elem || Z.n_cols != X.n_elem) throw std::invalid_argument("interp2(): Z must be Y.n_elem x X.n_elem");
+    mi_grid2* g = nullptr;
+    check(mi_grid2_create(dev.get(), X.memptr(), X.n_elem, Y.memptr(), Y.n_elem, Z.memptr(), 0u, &g), dev.get(),
+          "mi_grid2_create");
+    ZI.set_size(YI.n_elem, XI.n_elem);
+    mi_status st = mi_interp2_grid_nearest_f64_host(dev.get(), g, XI.memptr(), XI.n_elem, YI.memptr(), YI.n_elem, ZI.memptr(),
+                                                    extrap_val);
+    mi_grid2_destroy(g);
+    check(st, dev.get(), "mi_interp2_grid_nearest_f64_host");
+}
+
+// an integer extrapolation value (a literal 0 among them) still means the linear overloads: without these the null
+// pointer conversion to `const char* method` would compete with the conversion to double.  One per kind of ZI: where
+// arma::vec derives from arma::mat, a guard for arma::mat alone would tie with the scattered overload on an arma::vec ZI.
+template <typename T, typename std::enable_if<std::is_integral<T>::value, int>::type = 0>
+inline void interp2(const arma::vec& X, const arma::vec& Y, const arma::mat& Z, const arma::vec& XI, const arma::vec& YI,
+                    arma::mat& ZI, T extrap_val, Device& dev = Device::instance())
+{
+    interp2(X, Y, Z, XI, YI, ZI, (double)extrap_val, dev);
+}
+
+template <typename T, typename std::enable_if<std::is_integral<T>::value, int>::type = 0>
+inline void interp2(const arma::vec& X, const arma::vec& Y, const arma::mat& Z, const arma::vec& XI, const arma::vec& YI,
+                    arma::vec& ZI, T extrap_val, Device& dev = Device::instance())
+{
+    interp2(X, Y, Z, XI, YI, ZI, (double)extrap_val, dev);
 }
 
 // RestrictKernel (EventDrivenMap.cu:769-785) on host vectors: position at t = final_time from the last event

@@ -50,6 +50,17 @@
  *     that their rounded distances to q are equal (X = [0, 2^-60, 1, 2], q = 1:
  *     1 - 0 and 1 - 2^-60 round to the same double) the scan stops there (node 0)
  *     and the rule returns the true nearest node (node 2).  DESIGN.md section 2.
+ *   - 2-D nearest rule shared by every interp2 "nearest" entry point (arma::interp2's
+ *     "nearest" is separable: interp2_helper_nearest along one axis, then along the
+ *     other, so the 1-D rule per axis is the 2-D rule):
+ *        kx = nearest-rule node of XI[j] on the x axis     (the 1-D rule, unchanged: bracket l, r = min(l+1, n-1),
+ *        ky = nearest-rule node of YI[i] on the y axis      a = q - X[l], b = X[r] - q, k = (b < a) ? r : l; a tie keeps the LEFT node)
+ *        either coordinate NaN                 -> NaN                      (NaN wins over out-of-range)
+ *        else either coordinate out of range   -> extrap_val
+ *        else                                  -> Z(ky, kx), the stored 64 bits: inf, NaN, -0.0 and denormals as they are
+ *     A special value in Z reaches exactly the outputs whose (ky, kx) is its node.
+ *     XI and YI may be in any order (Armadillo demands ascending order; the linear
+ *     calls here do not, and neither do these).
  */
 #ifndef MI355_INTERP_H
 #define MI355_INTERP_H
@@ -93,7 +104,10 @@ extern "C" {
  *                and counter under a second name, and the phased kernel on its own for tests);
  *                mi_debug_interp1_phased_sweep_ex, mi_debug_sweep_partition (the phase classes set apart by work
  *                instead of a clock wait: the kernel on its own with a first-tile table and optional clock stamps,
- *                and the ownership function, csrc/mi_sweep_partition.hpp, on the host) */
+ *                and the ownership function, csrc/mi_sweep_partition.hpp, on the host);
+ *                mi_interp2_nearest_f64_dev, mi_interp2_grid_nearest_f64_dev, mi_interp2_grid_nearest_f64_host,
+ *                mi_interp2_slices_nearest_f64_dev, mi_debug_nearest2_launches (arma::interp2's "nearest" method:
+ *                scattered pairs and the gridded output on a mi_grid2, and the gridded output over the slices of a cube) */
 #define MI355_INTERP_ABI_VERSION 4
 
 typedef int mi_status;
@@ -155,6 +169,11 @@ size_t mi_debug_nearest_launches(int form);
  * with 16-B accesses, 1 rows tile body with 8-B accesses, 2 rows flat body (m < 256) -- mi_interp1_rows_nearest_f64_dev;
  * 3 pairs LDS form (n <= 4096), 4 pairs direct form -- mi_interp1_pairs_nearest_f64_dev; 0 for any other value of form. */
 size_t mi_debug_nearest_batched_launches(int form);
+/* Test hook: calls of the interp2 nearest entry points by this process so far that took the given form: 0 scattered --
+ * mi_interp2_nearest_f64_dev; 1 tile body with 16-B stores, 2 tile body with 8-B stores, 3 flat body (nyi < 256) with 16-B
+ * stores, 4 flat body with 8-B stores -- mi_interp2_grid_nearest_f64_dev (and each chunk of its _host form); 5 tile body
+ * with 16-B stores, 6 tile body with 8-B stores, 7 flat body -- mi_interp2_slices_nearest_f64_dev; 0 for any other value. */
+size_t mi_debug_nearest2_launches(int form);
 /* Test hook: which closed form of the abscissae a mode-0 table evaluates (0 fma(i, dx, x0); 1 x0 + i*dx;
  * 2 x0 + span*(i/(n-1)); 3 the same with the quotient from a Markstein step) and whether its last node is pinned to
  * xmax -- i.e. which instance of the interp1 kernels a call on this table launches.  Both are -1 for the {x,y} modes. */
@@ -296,7 +315,7 @@ mi_status mi_interp1_f64(mi_ctx* ctx, const double* x, const double* y, size_t n
  * sweep orders such queries by table region; ordered or clustered queries, and tables that fit L2, stream as the linear
  * call does.  Many tables at once: one X, a table per column -> mi_interp1_cols_nearest_f64_dev; one X, a table per ROW
  * or the slices of a cube -> mi_interp1_rows_nearest_f64_dev; an X per column -> mi_interp1_pairs_nearest_f64_dev.
- * There is no nearest form of the each, rowpairs and slices calls. */
+ * There is no nearest form of the each and rowpairs calls. */
 mi_status mi_interp1_nearest_f64_dev(mi_ctx* ctx, const mi_grid1* g, const double* xq_dev, double* yq_dev,
                                      size_t nq, double extrap_val);
 /* host pointers, synchronous: the chunked, pinned path of mi_interp1_f64_host around the nearest kernels */
@@ -335,6 +354,34 @@ mi_status mi_interp2_grid_f64_dev(mi_ctx* ctx, const mi_grid2* g, const double* 
                                   const double* yi_dev, size_t nyi, double* zi_dev, double extrap_val);
 mi_status mi_interp2_grid_f64_host(mi_ctx* ctx, const mi_grid2* g, const double* xi, size_t nxi,
                                    const double* yi, size_t nyi, double* zi, double extrap_val);
+/* Which call when: pairs in no pattern -> mi_interp2_f64_dev; every combination of two query axes -> the gridded call
+ * (each coordinate located once).  The value of the nearest node in place of the blend (label maps, masks, material
+ * indices, a field with a NaN cell that must not spread) -> the nearest twins below. */
+
+/* ---- arma::interp2's "nearest" method on a mi_grid2 -----------------------
+ * The 2-D nearest rule at the top of this header in place of the blend: zq[i] = Z(ky, kx), a copy of one table element,
+ * read from the resident (repacked) table of the linear calls -- the same handles, either layout, no second copy of Z.
+ * Each call takes its linear twin's signature and its contract word for word: argument checks and status codes, 8-B
+ * alignment, empty calls (nq == 0; nxi == 0 or nyi == 0) MI_OK with nothing launched or written, the overflow checks,
+ * _dev asynchronous on the context's stream, _host synchronous.  xi, yi, xq, yq may be in any order.
+ *   mi_interp2_nearest_f64_dev        scattered pairs (mi_interp2_f64_dev): one 8-B gather per query.
+ *   mi_interp2_grid_nearest_f64_dev   gridded (mi_interp2_grid_f64_dev), zi column-major nyi x nxi,
+ *                                     zi[i + j*nyi] == what mi_interp2_nearest_f64_dev returns for (xi[j], yi[i]), bit for
+ *                                     bit.  Each coordinate becomes one 4-B record (node, or a flag) in the context's
+ *                                     record workspace, shared in stream order with the linear calls: linear and nearest
+ *                                     calls back to back do not disturb each other.  One 8-B read per output where the
+ *                                     bilinear call reads 32 B, and none while the table column stays the same.
+ *   mi_interp2_grid_nearest_f64_host  host pointers, synchronous: upload, the device call, download; beyond 2 x 8 Mi
+ *                                     outputs in column chunks of about 8 Mi outputs on the context's own stream (no
+ *                                     pinning, no second stream: the path is PCIe-bound either way).
+ * Kernels: csrc/mi_nearest2.hip; mi_debug_nearest2_launches tells which body ran.  Timings against the linear twins:
+ * not measured yet.  There are no group forms and no host form of the scattered call. */
+mi_status mi_interp2_nearest_f64_dev(mi_ctx* ctx, const mi_grid2* g, const double* xq_dev,
+                                     const double* yq_dev, double* zq_dev, size_t nq, double extrap_val);
+mi_status mi_interp2_grid_nearest_f64_dev(mi_ctx* ctx, const mi_grid2* g, const double* xi_dev, size_t nxi,
+                                          const double* yi_dev, size_t nyi, double* zi_dev, double extrap_val);
+mi_status mi_interp2_grid_nearest_f64_host(mi_ctx* ctx, const mi_grid2* g, const double* xi, size_t nxi,
+                                           const double* yi, size_t nyi, double* zi, double extrap_val);
 
 /* ---- interp1 over the columns of a matrix (one X, many Y) ---------------
  * MATLAB's interp1 with a matrix Y; arma::interp1 takes vectors only, so this is the loop over the columns of an
@@ -490,11 +537,28 @@ mi_status mi_interp1_each_f64_host(mi_ctx* ctx, const double* x, size_t ldx, con
  * ldzi < nyi, a slice stride smaller than its matrix (nslices > 1), sizes whose byte counts overflow.
  * There is no host-pointer or group form of this call yet.
  * Which call when: one table that answers many calls -> mi_grid2 and mi_interp2_grid_f64_dev (its resident layout gives
- * one 32-B cell per output); a Z that changes on the device, or many slices over one pair of axes -> this call. */
+ * one 32-B cell per output); a Z that changes on the device, or many slices over one pair of axes -> this call.  The
+ * value of the nearest node in place of the blend -> mi_interp2_slices_nearest_f64_dev. */
 mi_status mi_interp2_slices_f64_dev(mi_ctx* ctx, const mi_axis1* ax, const mi_axis1* ay, const double* z_dev, size_t ldz,
                                     size_t z_slice_stride, size_t nslices, const double* xi_dev, size_t nxi,
                                     const double* yi_dev, size_t nyi, double* zi_dev, size_t ldzi, size_t zi_slice_stride,
                                     double extrap_val);
+/* The "nearest" method over the slices of a cube: mi_interp2_slices_f64_dev's contract word for word (layouts, argument
+ * checks and status codes, 8-B alignment, the axis-device check, the overflow checks, both strides ignored for
+ * nslices <= 1, empty calls MI_OK with nothing launched or written, rows ny..ldz-1 of z and the gap between slices never
+ * read, rows nyi..ldzi-1 of zi and the gap between slices never written, asynchronous on the context's stream) with the
+ * 2-D nearest rule in place of the blend:
+ *     zi[i + j*ldzi + s*zi_slice_stride] == z[ky + kx*ldz + s*z_slice_stride],  the stored 64 bits,
+ * bit-identical to mi_interp2_grid_nearest_f64_dev on a mi_grid2 built from (x, y, Z_s).  A special value in one slice
+ * reaches the outputs of that slice whose (ky, kx) is its node and nothing else.  Each coordinate is located once per call
+ * for all slices (4-B records in the context's record workspace, shared in stream order with the linear calls); one
+ * kernel follows, which gathers through L2 for every slice size: one 8-B read per output where the linear call reads
+ * four corners, so there is no LDS form (csrc/mi_nearest2.hip; mi_debug_nearest2_launches: 5 / 6 / 7).  Timing against
+ * the linear LDS form for small slices: not measured yet. */
+mi_status mi_interp2_slices_nearest_f64_dev(mi_ctx* ctx, const mi_axis1* ax, const mi_axis1* ay, const double* z_dev, size_t ldz,
+                                            size_t z_slice_stride, size_t nslices, const double* xi_dev, size_t nxi,
+                                            const double* yi_dev, size_t nyi, double* zi_dev, size_t ldzi,
+                                            size_t zi_slice_stride, double extrap_val);
 
 /* ---- interp1 along the rows of a matrix / across the slices of a cube -------
  * mi_interp1_cols_f64_dev for data stored the other way round: one table per ROW of a column-major matrix.  An ensemble
